@@ -15,9 +15,12 @@ Rank 0 prints ONE JSON line.  Extra objects:
                algorithmic bytes/MACs of its launches (SURVEY.md §8d counting rule: input + output +
                weight elements per layer) / their duration measured with hipEvents on the launch
                stream (ptta_profile); roofline_by_class: the same for every launch class of the step.
-  timing       SURVEY.md §8d / BASELINE.md §4: whatever --steps says, >= 10 blocks of K steps so that
-               >= 200 steps are timed (each block bracketed by barrier + synchronize, MAX over ranks);
-               ms_per_step = MEDIAN over the blocks, min / max beside it.
+  timing       exactly K = --steps timed steps, split into min(10, K) blocks of near-equal size (each block
+               bracketed by barrier + synchronize, MAX over ranks); ms_per_step = MEDIAN over the blocks of
+               the block's time per step, min / max beside it.  Choose K >= 200 for a BASELINE.md §4 figure.
+  --dump-outputs DIR  after the timed steps, what the LAST timed step handed its caller, as DIR/<name>.npy
+               (float32): loss_info and the adapted parameters with their Adam moments.  Inputs are seeded:
+               two builds run with the same arguments can be compared output for output.
   cpu_baseline the oracle (PyTorch CPU restatement, oracle/proxytta_oracle.py) timed on this
                box's host cores on a bounded sample (rank 0, N=1 only).
 """
@@ -61,6 +64,23 @@ DTYPE_TEXT = {
     'mixed': ('mixed: real frames\' forward (the scored depth) f32 storage + bf16x3 MFMA arithmetic; no_grad proxy pass and all data gradients bf16 '
               'storage + single bf16 MFMA; fp32 accumulate everywhere; loss / Adam / adapted parameters fp32 (include/ptta.h PTTA_DTYPE_MIXED)'),
 }
+
+
+def timed_blocks(steps, single_block=False):
+    """Block sizes of the timed region: exactly `steps` steps in all, min(10, steps) blocks (one with single_block)."""
+    nb = 1 if single_block else min(10, steps)
+    return [steps // nb + (1 if b < steps % nb else 0) for b in range(nb)]
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy in float32 ('/' in a name becomes '__')."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(path, name.replace('/', '__') + '.npy'), a)
+    assert total <= 64 << 20, 'dump of %d bytes exceeds 64 MB' % total
 
 
 def cpu_model_string():
@@ -546,15 +566,16 @@ def msgchn_multi_stream(args, rank, world, dist, affinity):
                     info, _ = e.step(*frames[k][(it0 + it) % 4], next_frame=frames[k][(it0 + it + 1) % 4])
         return info
     run(args.warmup, 0)
-    nblocks = 1 if args.single_block else max(10, -(-200 // max(args.steps, 1)))
+    blocks = timed_blocks(args.steps, args.single_block)
+    nblocks = len(blocks)
     block_s, own_block_s, it = [], [], args.warmup
-    for blk in range(nblocks):
+    for k_steps in blocks:
         barrier()
         t0 = time.perf_counter()
-        info = run(args.steps, it)
-        it += args.steps
+        info = run(k_steps, it)
+        it += k_steps
         barrier()
-        dt = time.perf_counter() - t0
+        dt = (time.perf_counter() - t0) * args.steps / k_steps        # scaled to a block of --steps steps
         own_block_s.append(dt)
         if dist is not None:
             t = torch.tensor([dt], device='cuda' if dist.get_backend() == 'nccl' else 'cpu', dtype=torch.float64)
@@ -582,7 +603,7 @@ def msgchn_multi_stream(args, rank, world, dist, affinity):
                        'parallelism': 'independent frame streams, dp%d x %d streams per GPU, no collectives' % (world, S), 'streams_per_gpu': S,
                        'note': 'NOT the headline configuration (one stream per GPU): ms_per_step is per frame over all streams of a GPU',
                        'cpu_affinity': affinity, 'finite': finite},
-            'timing': {'blocks': nblocks, 'steps_timed': nblocks * args.steps * S, 'ms_per_frame_min': 1e3 * min(block_s) / (S * args.steps),
+            'timing': {'blocks': nblocks, 'steps_timed': args.steps * S, 'ms_per_frame_min': 1e3 * min(block_s) / (S * args.steps),
                        'ms_per_frame_max': 1e3 * max(block_s) / (S * args.steps),
                        'per_rank_ms_per_step': {'min': min(per_rank_ms), 'median': float(np.median(per_rank_ms)), 'max': max(per_rank_ms), 'ranks': per_rank_ms,
                                                 'note': "each rank's own median block / steps (S frames per step), before the MAX over ranks"}}}))
@@ -833,7 +854,9 @@ def main():
                     help="'mixed' (default): BASELINE config 2 -- the scored depth's tensors fp32 / bf16x3, the no_grad proxy pass, the heads and the "
                          "data gradients bf16 / single MFMA (include/ptta.h PTTA_DTYPE_MIXED); 'fp32': every tensor fp32 / bf16x3")
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--single-block', action='store_true', help='time ONE block of --steps steps (quick A/B runs) instead of >= 10 blocks / >= 200 steps')
+    ap.add_argument('--single-block', action='store_true', help='time the --steps steps as ONE block instead of min(10, K) blocks')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step returned to its caller as DIR/<name>.npy (float32, < 64 MB)')
     ap.add_argument('--no-self-check', action='store_true', help='skip the pipelined-vs-plain bitwise replay on fresh handles')
     ap.add_argument('--no-nlspn', action='store_true', help='skip the side measurements (2layers, NLSPN, CostDCNet)')
     ap.add_argument('--streams-per-gpu', type=int, default=1,
@@ -845,6 +868,10 @@ def main():
                     help='tests only: run launcher / rendezvous / barrier / max-over-ranks / JSON with NO device work '
                          '(value is null, "data": "none"); lets the multi-rank path run on a CPU box with gloo')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    if args.dump_outputs and (args.workload != 'msg_chn' or args.streams_per_gpu > 1 or args.plumbing_only):
+        ap.error('--dump-outputs is implemented for the headline workload only (--workload msg_chn, one stream per GPU)')
 
     if 'RANK' not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
@@ -880,8 +907,9 @@ def main():
     eng = Engine(1, H, W, dtype=args.dtype, keep=keep, options=options, **HP)
     sd = {k: torch.from_numpy(np.asarray(v)).cuda() for k, v in synth.formula_state_dict(MODE).items()}
     eng.load_state_dict(sd)
+    moments = {name: (torch.zeros_like(sd[name]), torch.zeros_like(sd[name])) for name in ADAPTED}
     for name in ADAPTED:
-        eng.bind_adapted(name, sd[name], torch.zeros_like(sd[name]), torch.zeros_like(sd[name]))
+        eng.bind_adapted(name, sd[name], *moments[name])
     nframes = 4     # this rank's slice of the frame stream, resident in HBM before the timed region
     frames = [[torch.from_numpy(x).cuda() for x in synth.synthetic_frame(rank * 1000 + i, H, W, 1)] for i in range(nframes)]
 
@@ -901,20 +929,22 @@ def main():
         return frames[(i + 1) % nframes] if pipe else None
     for i in range(args.warmup):
         eng.step(*frames[i % nframes], next_frame=nxt(i))
-    # >= 10 blocks of K steps, >= 200 timed steps in all; every block is the contract's timed region: barrier + synchronize on
-    # both sides, MAX over ranks; the reported figure is the MEDIAN block.  (With --warmup 0 the first timed call computes its own prefix in line.)
-    nblocks = 1 if args.single_block else max(10, -(-200 // max(args.steps, 1)))
+    # exactly K = --steps timed steps in min(10, K) blocks; every block is the contract's timed region: barrier + synchronize on both sides,
+    # MAX over ranks; the reported figure is the MEDIAN block, each block's time scaled to K steps.  (With --warmup 0 the first timed call
+    # computes its own prefix in line.)
+    blocks = timed_blocks(args.steps, args.single_block)
+    nblocks = len(blocks)
     block_s, own_block_s = [], []
     info = None
     it = args.warmup
-    for blk in range(nblocks):
+    for k_steps in blocks:
         barrier()
         t0 = time.perf_counter()
-        for i in range(args.steps):
+        for i in range(k_steps):
             info, _ = eng.step(*frames[it % nframes], next_frame=nxt(it))
             it += 1
         barrier()
-        dt = time.perf_counter() - t0
+        dt = (time.perf_counter() - t0) * args.steps / k_steps
         own_block_s.append(dt)
         if dist is not None:
             t = torch.tensor([dt], device='cuda' if dist.get_backend() == 'nccl' else 'cpu', dtype=torch.float64)
@@ -922,6 +952,10 @@ def main():
             dt = float(t.item())
         block_s.append(dt)
     elapsed = float(np.median(block_s))
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: loss_info and, updated in place, the adapted parameters and their Adam moments
+        dump_outputs(args.dump_outputs, dict([('loss_info', info)] + [(k, sd[k]) for k in ADAPTED] +
+                                             [(k + '.exp_avg', moments[k][0]) for k in ADAPTED] + [(k + '.exp_avg_sq', moments[k][1]) for k in ADAPTED]))
     # per-rank view of the same blocks (each rank's OWN median block, gathered): tells a slow rank from a slow barrier in a SCALE run
     per_rank_ms = [1e3 * float(np.median(own_block_s)) / args.steps]
     if dist is not None:
@@ -935,13 +969,13 @@ def main():
         for i in range(3):
             eng.step(*frames[i % nframes])
         pb = []
-        for blk in range(nblocks):
+        for k_steps in blocks:
             torch.cuda.synchronize()
             tp = time.perf_counter()
-            for i in range(args.steps):
+            for i in range(k_steps):
                 eng.step(*frames[i % nframes])
             torch.cuda.synchronize()
-            pb.append(1e3 * (time.perf_counter() - tp) / args.steps)
+            pb.append(1e3 * (time.perf_counter() - tp) / k_steps)
         plain_ms = float(np.median(pb))
     # the all-fp32 mode beside the headline (same protocol, fresh handle): what the mixed mode buys on this box in this run
     other_dtype_ms, graph_ms = None, None
@@ -955,13 +989,13 @@ def main():
         for i in range(max(args.warmup, 3)):
             e2.step(*frames[i % nframes], next_frame=nxt(i))
         ob = []
-        for blk in range(min(nblocks, 5)):
+        for k_steps in blocks[:5]:
             torch.cuda.synchronize()
             tp = time.perf_counter()
-            for i in range(args.steps):
+            for i in range(k_steps):
                 e2.step(*frames[i % nframes], next_frame=nxt(i))
             torch.cuda.synchronize()
-            ob.append(1e3 * (time.perf_counter() - tp) / args.steps)
+            ob.append(1e3 * (time.perf_counter() - tp) / k_steps)
         e2.close()
         return float(np.median(ob)), len(ob)
     if world == 1 and not args.no_self_check:
@@ -1108,8 +1142,9 @@ def main():
                               'mfma_frac_note': 'issued bf16 MFMA FLOP (bf16x3 launches counted 3x, single-MFMA launches 1x) / 2.5 PFLOP/s dense'},
             'roofline': roof,
             'roofline_by_class': by_class,
-            'timing': {'protocol': '%d blocks x %d steps, each block bracketed by barrier + synchronize, MAX over ranks; ms_per_step = median block' % (nblocks, args.steps),
-                       'blocks': nblocks, 'steps_timed': nblocks * args.steps, 'ms_per_step_median': 1e3 * elapsed / args.steps,
+            'timing': {'protocol': '%d timed steps in %d blocks (%s), each block bracketed by barrier + synchronize, MAX over ranks; ms_per_step = median block'
+                                   % (args.steps, nblocks, '+'.join(map(str, blocks))),
+                       'blocks': nblocks, 'steps_timed': args.steps, 'ms_per_step_median': 1e3 * elapsed / args.steps,
                        'ms_per_step_min': 1e3 * min(block_s) / args.steps, 'ms_per_step_max': 1e3 * max(block_s) / args.steps,
                        'per_rank_ms_per_step': {'min': min(per_rank_ms), 'median': float(np.median(per_rank_ms)), 'max': max(per_rank_ms),
                                                 'ranks': per_rank_ms, 'note': "each rank's own median block, before the MAX over ranks"}},

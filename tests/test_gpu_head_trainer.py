@@ -137,23 +137,48 @@ def test_head_trainer_reproduces_reference(golden_dir, name, mode):
             _check(z, last + k, sd[k], 1e-5, 1e-6, k)
 
 
+def _rel_dev(a, b):
+    """(worst |a - b| / largest |b|, mean |a - b| / mean |b|)"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    d = np.abs(a - b)
+    return d.max() / np.abs(b).max(), d.mean() / np.abs(b).mean()
+
+
 @pytest.mark.parametrize('mode', MODES)
 def test_head_trainer_against_oracle_other_shape(mode):
-    """A shape and batch the fixtures do not hold, 2 steps each loss type, incl. the EMA and the step counter."""
+    """A shape and batch the fixtures do not hold, 2 steps each loss type, incl. the EMA and the step counter.
+    Gradients are held to an fp64 evaluation of the same steps.  After Adam's first step a hidden pre-activation of this case lands within
+    fp32 rounding of zero (9e-8 from it after frame 10): which side of the ReLU it takes depends on the summation order (it differs between
+    CPU thread counts), and one flipped row moves that unit's gradients by 1/720 -- the fp32 oracle then sits 7e-4 (mean) from the fp64
+    evaluation.  So the bound is GRAD_TOL or twice the fp32 oracle's own distance from fp64, whichever is larger (as for the CostDCNet
+    fixtures, make_golden_costdcnet_fp64.py): on a well-conditioned step that is GRAD_TOL itself."""
     n, h, w = 3, 48, 80
     hp = dict(lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0)
     for loss_type in ('head_selfsup_seq_ema_reverse', 'head_selfsup_seq_ema'):
         eng, sd, sd_np, _ = make_head_engine(n, h, w, hp, 0.99, mode=mode)
         o = HO.HeadTrainerOracle(sd_np, loss_type, max_input_depth=80.0, tau=0.99, **hp)
+        sd64 = {k: (torch.from_numpy(np.asarray(v)).double() if np.asarray(v).dtype == np.float32 else torch.from_numpy(np.asarray(v)))
+                for k, v in sd_np.items()}
+        o64 = HO.HeadTrainerOracle(sd64, loss_type, max_input_depth=80.0, tau=0.99, **hp)
         for s in range(2):
             image, sparse = synth.synthetic_frame(10 + s, h, w, n)
             r = o.step(torch.from_numpy(image), torch.from_numpy(sparse))
+            r64 = o64.step(torch.from_numpy(image).double(), torch.from_numpy(sparse).double())
             emb, ref = eng.head_forward(torch.from_numpy(image).cuda(), torch.from_numpy(sparse).cuda(), 'reverse' in loss_type)
             loss = eng.head_backward()
             assert abs(float(loss) - r['loss']) < (2e-5 if s == 0 else 1e-4)
-            for k, g in r['grads'].items():
-                mine = eng.head_grad(k, sd[k]).cpu()
-                _grad_close(mine.numpy(), g.numpy(), s == 0, k, mode)
+            assert set(r['grads']) == set(r64['grads'])
+            for k, g in r64['grads'].items():
+                mine = eng.head_grad(k, sd[k]).cpu().numpy()
+                g = g.numpy()
+                if np.abs(g).max() < 1e-8:
+                    _grad_close(mine, g, s == 0, k, mode)          # mathematically zero: the fp32 oracle's rounding noise is not a yardstick
+                    continue
+                tmax, tmean = GRAD_TOL[mode][s == 0]
+                omax, omean = _rel_dev(r['grads'][k].numpy(), g)
+                dmax, dmean = _rel_dev(mine, g)
+                assert dmax <= max(tmax, 2 * omax) + 1e-12, (k, s, dmax, tmax, omax)
+                assert dmean <= max(tmean, 2 * omean) + 1e-12, (k, s, dmean, tmean, omean)
             eng.head_adam_step()
         for k in HEAD_TARGETS:
             np.testing.assert_allclose(sd[k].cpu().numpy(), o.P[k].detach().numpy(), rtol=1e-5, atol=0.01 * 2.5 * 5e-4 * 4 + 1e-7, err_msg=k)
