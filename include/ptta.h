@@ -427,6 +427,15 @@ int ptta_debug_tensor(ptta_handle h, const char* name, float* dst, int64_t capac
 int ptta_op_conv32(const float* in_nhwc, const float* weight, const float* bias, float* out_nhwc,
                    int b, int hin, int win, int mode, int relu_in, int in_major, int flip, int dtype, int naive,
                    ptta_stream s);
+/* Diagnostic (tests, tools/bench_gwgrad_wide.py): weight and bias gradient of a stride-1 3x3 convolution, dense fp32 NHWC device maps
+ * x [b][h][w][ci] and gy [b][h][w][co], 1 <= ci, co <= 256 -> gw [co][ci][3][3], gb [co] (gb may be null).  impl 0: the launcher the engine
+ * runs -- bf16x3 on the matrix cores (hi*hi + hi*lo + lo*hi, fp32 accumulation) for Ci, Co <= 64, 32 <-> 128 and, for channel counts that
+ * are multiples of 16 up to 256 with more than one 32 x 32 tile pair (16 -> 64, 48 <-> 256), the wide form; the fp32-MFMA form otherwise;
+ * impl 1: the fp32-MFMA form for every shape; impl 2: the direct fp32 form of PTTA_CONV_IMPL=naive.  Deterministic: fixed-order
+ * reduction, no atomics.  reps > 0: `reps` more calls of the same form timed with hipEvents on s, microseconds per call (weight-gradient
+ * kernel + its reduction) to *us_per_call_host; reps = 0 and us_per_call_host = NULL compute once.  Synchronises. */
+int ptta_op_gwgrad(const float* x_nhwc, const float* gy_nhwc, float* gw, float* gb, int b, int h, int w, int ci, int co, int impl,
+                   int reps, float* us_per_call_host, ptta_stream s);
 /* Diagnostic (tools/bench_chain.py): `reps` dependent launches of one stride-1 32->32 convolution (fp32 NHWC, default arithmetic) captured
  * into one hipGraph and replayed `replays` times: microseconds per launch INSIDE a replayed graph.  epi_flags: 2 = ReLU mask from `aux`,
  * 4 = skip addition of `aux`, 8 = the same chain launched directly (no graph), 16 = the layer loop (ONE launch per `reps` layers with a

@@ -661,12 +661,20 @@ __device__ __forceinline__ void wsplit8(const float* v, uint4& hi, uint4& lo) {
 // BLKRED (single only): the four waves' partial tiles are summed inside the block in a fixed tree ((w0 + w2) + (w1 + w3)) through LDS and the
 // block writes ONE partial -- four times the waves for the same partial traffic: the launch is a latency chain of ~2 us per item and wave
 // (38 strided loads, then 27 MFMAs), so its duration is the items per wave.
-template <bool GY16, bool BLKRED = false>          // GY16: gy.p points at bf16 values (the narrow gradient maps of the MSG_CHN mixed mode): widened on load, the same products
+// WIDE (channel counts up to 256 x 256 outside the forms above: NLSPN's 48 <-> 256 and CostDCNet's 16 -> 64 of the 2layers meta block):
+// grid (item chunks, pair groups); the ncib x ncob tile pairs, pair = cob * ncib + cib, are taken four per block (blockIdx.y = group of
+// four consecutive pairs; waves past the last pair return), or -- fewer than four pairs -- wpp = 4 / npairs waves per pair that split its
+// items.  Partials [chunk = blockIdx.x * wpp + sub][pair], the layout of gwgrad_mfma_kernel (same reducer, npairs of them per chunk).
+template <bool GY16, bool BLKRED = false, bool WIDE = false>  // GY16: gy.p points at bf16 values (the narrow gradient maps of the MSG_CHN mixed mode): widened on load, the same products
 __global__ __launch_bounds__(256) void gwgrad_x3_kernel(GView x, GView gy, int nitems_x, int single, int ncib, float* __restrict__ part) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & 31, hg = lane >> 5;
+    const int npairs = WIDE ? ncib * ((gy.C + 31) >> 5) : 4;
+    const int wpp = WIDE && npairs < 4 ? 4 / npairs : 1;                   // waves per pair (WIDE only)
+    const int pair = WIDE ? (int)blockIdx.y * (4 / wpp) + wave / wpp : wave, sub = WIDE ? wave % wpp : 0;
+    if (WIDE && pair >= npairs) return;                                   // (wave-uniform; no barrier in this form)
     // the four waves of a block = the four (ci tile, co tile) pairs: 2 x 2 (<= 64 x 64 channels), 1 x 4 (32 -> 128) or 4 x 1 (128 -> 32)
-    const int cob = single ? 0 : wave / ncib, cib = single ? 0 : wave % ncib;
+    const int cob = single ? 0 : pair / ncib, cib = single ? 0 : pair % ncib;
     const int H = x.H, W = x.W;
     const int co = cob * 32 + c, ci = cib * 32 + c;
     const bool cov = co < gy.C, civ = ci < x.C;
@@ -771,8 +779,8 @@ __global__ __launch_bounds__(256) void gwgrad_x3_kernel(GView x, GView gy, int n
         }
     };
     Regs r0, r1;
-    const int stride = single ? (int)gridDim.x * 4 : (int)gridDim.x;
-    int item = single ? (int)blockIdx.x * 4 + wave : (int)blockIdx.x;
+    const int stride = single ? (int)gridDim.x * 4 : (int)gridDim.x * wpp;
+    int item = single ? (int)blockIdx.x * 4 + wave : (int)blockIdx.x * wpp + sub;
     if (item < nitems) fetch(item, r0);
     while (item < nitems) {
         const int n1 = item + stride;
@@ -812,7 +820,8 @@ __global__ __launch_bounds__(256) void gwgrad_x3_kernel(GView x, GView gy, int n
         put(part + (long)blockIdx.x * GWG_PART);
         return;
     }
-    float* out = part + ((long)blockIdx.x * 4 + wave) * GWG_PART;      // pair index = cob * ncib + cib = wave; single: chunk index
+    // pair index = cob * ncib + cib = wave; single: chunk index; WIDE: chunk blockIdx.x * wpp + sub, npairs partials per chunk
+    float* out = part + (WIDE ? ((long)blockIdx.x * wpp + sub) * npairs + pair : (long)blockIdx.x * 4 + wave) * GWG_PART;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
@@ -959,8 +968,9 @@ int ptta_launch_gconv_x3_strided(const GX3Args& a, int ks, int mode, int hin, in
 
 int ptta_gwgrad_mfma_chunks(long pixels) { long n = (pixels + 127) / 128; return (int)(n > 1024 ? 1024 : (n < 1 ? 1 : n)); }
 long ptta_gwgrad_mfma_part_floats(long pixels, int Ci, int Co) {
-    const long a = (long)ptta_gwgrad_mfma_chunks(pixels) * ((Ci + 31) / 32) * ((Co + 31) / 32) * GWG_PART;
-    const long b = 256L * 4 * GWG_PART;                                  // gwgrad_x3_kernel: 256 blocks x 4 tile pairs
+    const long np = (long)((Ci + 31) / 32) * ((Co + 31) / 32);
+    const long a = (long)ptta_gwgrad_mfma_chunks(pixels) * np * GWG_PART;
+    const long b = 256L * (np > 4 ? np : 4) * GWG_PART;                  // gwgrad_x3_kernel: 256 blocks x 4 tile pairs; WIDE: 256 chunks x npairs
     return a > b ? a : b;
 }
 int ptta_launch_gwgrad_mfma(const GView& x, const GView& gy, float* part, float* gw, float* gb, hipStream_t s, int gy_bf16, const GwAdam* adam) {
@@ -968,7 +978,25 @@ int ptta_launch_gwgrad_mfma(const GView& x, const GView& gy, float* part, float*
     const bool sq = x.C <= 64 && gy.C <= 64, wide_out = x.C <= 32 && gy.C <= 128, wide_in = x.C <= 128 && gy.C <= 32;
     // (the bf16x3 kernel addresses its maps with 32-bit byte offsets)
     const bool small_maps = (double)x.B * x.H * x.W * x.ld * 4.0 < 4294967296.0 && (double)gy.B * gy.H * gy.W * gy.ld * 4.0 < 4294967296.0;
-    if ((sq || wide_out || wide_in) && x.C > 16 && small_maps) {
+    const int ncib = (x.C + 31) / 32, npairs = ncib * ((gy.C + 31) / 32);
+    const bool narrow_form = (sq || wide_out || wide_in) && x.C > 16;
+    // the Adam fused into the reduction exists for the single-pair form only: asked for anywhere else it is an error, not a silent no-update
+    if (adam && adam->pw && !(narrow_form && small_maps && x.C <= 32 && gy.C <= 32)) return -22;
+    // the WIDE form takes exactly the shapes that had only the fp32-MFMA form: channel counts multiples of 16 up to 256, at least two tile
+    // pairs (a single 16-channel pair -- CostDCNet's 1layer Conv2d(16, 16, 3) -- keeps the fp32-MFMA form)
+    if (!narrow_form && !gy_bf16 && small_maps && npairs >= 2 && !(x.C & 15) && !(gy.C & 15) && x.C <= 256 && gy.C <= 256) {
+        const int wpp = npairs < 4 ? 4 / npairs : 1, ngrp = npairs < 4 ? 1 : (npairs + 3) / 4;
+        const int nx = (x.W + 15) / 16;
+        const long nitems = (long)x.B * x.H * nx;
+        const long want = (nitems + wpp - 1) / wpp;
+        const int nblk = (int)(want < 256 ? want : 256);
+        const long n = 9L * x.C * gy.C + gy.C;
+        hipLaunchKernelGGL((gwgrad_x3_kernel<false, false, true>), dim3(nblk, ngrp), dim3(256), 0, s, x, gy, nx, 0, ncib, part);
+        hipLaunchKernelGGL(gwgrad_mfma_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64 * GWR_G), 0, s, part, nblk * wpp, npairs, ncib, x.C, gy.C, gw, gb, noad);
+        PTTA_CHECK_LAUNCH();
+        return 0;
+    }
+    if (narrow_form && small_maps) {
         // bf16x3 form: blocks of four waves = four 32x32 channel-tile pairs (2 x 2, or 1 x 4 / 4 x 1 for the 32 <-> 128 layers of the
         // 2layers meta block), partials [block][4 pairs]; <= 32 x 32 channels: one pair, the waves split the items, partials
         // [block * 4 + wave]
@@ -996,6 +1024,10 @@ int ptta_launch_gwgrad_mfma(const GView& x, const GView& gy, float* part, float*
         return 0;
     }
     if (gy_bf16) return -22;          // (the fp32-MFMA form takes fp32 gradients)
+    return ptta_launch_gwgrad_f32mfma(x, gy, part, gw, gb, s);
+}
+int ptta_launch_gwgrad_f32mfma(const GView& x, const GView& gy, float* part, float* gw, float* gb, hipStream_t s) {
+    const GwAdam noad{};
     const int nchunks = ptta_gwgrad_mfma_chunks((long)x.B * x.H * x.W);
     const int ncib = (x.C + 31) / 32, ncob = (gy.C + 31) / 32, npairs = ncib * ncob;
     hipLaunchKernelGGL(gwgrad_mfma_kernel, dim3(nchunks, npairs), dim3(64), 0, s, x, gy, nchunks, ncib, part);

@@ -2814,6 +2814,45 @@ int ptta_op_conv32(const float* in, const float* weight, const float* bias, floa
     return rc;
 }
 
+// Stand-alone weight + bias gradient of a stride-1 3x3 convolution on dense fp32 NHWC maps (tests, tools/bench_gwgrad_wide.py): the
+// engine's launcher (impl 0), the fp32-MFMA form (1) or the direct fp32 form of PTTA_CONV_IMPL=naive (2), then `reps` more launches of
+// the same form timed with hipEvents on `s`.
+int ptta_op_gwgrad(const float* x, const float* gy, float* gw, float* gb, int b, int h, int w, int ci, int co, int impl, int reps,
+                   float* us_per_call_host, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!x || !gy || !gw || b < 1 || h < 1 || w < 1 || ci < 1 || co < 1 || ci > 256 || co > 256 || impl < 0 || impl > 2 || reps < 0 ||
+        (reps > 0 && !us_per_call_host)) return -22;
+    GView xv, gv;
+    xv.p = (float*)x; xv.B = b; xv.H = h; xv.W = w; xv.C = ci; xv.ld = ci;
+    gv.p = (float*)gy; gv.B = b; gv.H = h; gv.W = w; gv.C = co; gv.ld = co;
+    const long P = (long)b * h * w;
+    const size_t nm = (size_t)ptta_gwgrad_mfma_part_floats(P, ci, co), nn = (size_t)ptta_gwgrad_slabs(P) * (9 * ci * co + co);
+    float* part = nullptr;
+    if (hipMalloc((void**)&part, (impl == 2 ? nn : nm) * 4) != hipSuccess) return -12;
+    auto run = [&]() {
+        return impl == 0 ? ptta_launch_gwgrad_mfma(xv, gv, part, gw, gb, s)
+                         : (impl == 1 ? ptta_launch_gwgrad_f32mfma(xv, gv, part, gw, gb, s) : ptta_launch_gwgrad(xv, gv, part, gw, gb, s));
+    };
+    int rc = run();
+    if (!rc && reps > 0) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = -5;
+        if (!rc) {
+            (void)hipEventRecord(e0, s);
+            for (int r = 0; r < reps && !rc; ++r) rc = run();
+            (void)hipEventRecord(e1, s);
+            (void)hipEventSynchronize(e1);
+            float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1);
+            *us_per_call_host = 1e3f * ms / (float)reps;
+        }
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    (void)hipFree(part);
+    return rc;
+}
+
 // Diagnostic: `reps` DEPENDENT launches of one 32 -> 32 stride-1 convolution (ping-pong between two buffers, optional ReLU mask / skip
 // addition epilogue reading a third) captured into ONE hipGraph and replayed: microseconds per launch as it costs INSIDE a replayed graph
 // (rocprofv3 adds ~3-5 us to every kernel and a host-timed single launch measures the launch path).  tools/bench_chain.py.

@@ -373,7 +373,10 @@ long ptta_gfrag_elems(int KK, int C0, int C1, int Co);
 int ptta_launch_gconv_x3(const GX3Args& a, int ks, hipStream_t s);
 int ptta_launch_gconv_x3_strided(const GX3Args& a, int ks, int mode, int hin, int win, hipStream_t s);
 long ptta_gwgrad_mfma_part_floats(long pixels, int Ci, int Co);
-// Adam applied by the weight gradient's reduction itself (gconv_mfma.hip gwgrad_mfma_reduce_kernel; <= 32 x 32 channels only): parameter + both
+// Adam applied by the weight gradient's reduction itself (gconv_mfma.hip gwgrad_mfma_reduce_kernel; <= 32 x 32 channels, the single-pair bf16x3 form only;
+// ptta_launch_gwgrad_mfma returns -22 for any other shape with ad.pw set): parameter + both
 // moments of the weight and of the bias, the hyper-parameter block, the device step count and its ticket (as ptta_launch_adam_multi)
 struct GwAdam { float *pw = nullptr, *mw = nullptr, *vw = nullptr, *pb = nullptr, *mb = nullptr, *vb = nullptr; const float* hyper = nullptr; int* step = nullptr; unsigned* ticket = nullptr; };
 int ptta_launch_gwgrad_mfma(const GView& x, const GView& gy, float* part, float* gw, float* gb, hipStream_t s, int gy_bf16 = 0, const GwAdam* adam = nullptr);
+// the fp32-MFMA form alone (gwgrad_mfma_kernel; ptta_launch_gwgrad_mfma takes it for the shapes no bf16x3 form covers): ptta_op_gwgrad's impl 1
+int ptta_launch_gwgrad_f32mfma(const GView& x, const GView& gy, float* part, float* gw, float* gb, hipStream_t s);

@@ -452,3 +452,25 @@ def op_conv32(x_nhwc, weight, bias, mode, relu_in=False, in_major=False, flip=Fa
     if rc != 0:
         raise RuntimeError('ptta_op_conv32 failed (%d)' % rc)
     return out
+
+
+GWGRAD_IMPLS = {'default': 0, 'fp32_mfma': 1, 'naive': 2}
+
+
+def op_gwgrad(x_nhwc, gy_nhwc, impl='default', with_bias=True, reps=0):
+    """Test / measurement hook: weight (and bias) gradient of a stride-1 3x3 convolution from fp32 NHWC device maps
+    x [b, h, w, ci] and gy [b, h, w, co] (include/ptta.h ptta_op_gwgrad).  impl: 'default' (the engine's launcher: bf16x3 wherever a
+    form exists), 'fp32_mfma' or 'naive'.  Returns (gw [co, ci, 3, 3], gb [co] or None, microseconds per call of `reps` timed calls)."""
+    lib = _lib.load()
+    b, h, w, ci = x_nhwc.shape
+    co = gy_nhwc.shape[3]
+    assert tuple(gy_nhwc.shape[:3]) == (b, h, w)
+    x_nhwc, gy_nhwc = x_nhwc.float().contiguous(), gy_nhwc.float().contiguous()
+    gw = torch.empty((co, ci, 3, 3), device=x_nhwc.device, dtype=torch.float32)
+    gb = torch.empty((co,), device=x_nhwc.device, dtype=torch.float32) if with_bias else None
+    us = ctypes.c_float(0.0)
+    rc = lib.ptta_op_gwgrad(ptr(x_nhwc), ptr(gy_nhwc), ptr(gw), ptr(gb), b, h, w, ci, co,
+                            GWGRAD_IMPLS[impl], int(reps), byref(us), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_gwgrad failed (%d)' % rc)
+    return gw, gb, (us.value if reps > 0 else None)
