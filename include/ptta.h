@@ -34,7 +34,7 @@ typedef void* ptta_stream;              /* hipStream_t */
 
 /* PTTA_BACKBONE_NLSPN: ExternalModel_Adapt(model_name='nlspn') -- src/nlspn_model_adapt.py:13-128 ->
  * NLSPNModel_Adapt._rgbd_meta_contrast (external_src/NLSPN/src/model/nlspnmodel_adapt.py:850-944), adapter settings of
- * src/nlspn_model_adapt.py:56-68, adapt_parameters('meta_bn') (:322-337).  meta_mode must be PTTA_META_1LAYER (optionally | PTTA_NLSPN_LEGACY_OFFSET), dtype
+ * src/nlspn_model_adapt.py:56-68, adapt_parameters('meta_bn') (:322-337).  meta_mode PTTA_META_1LAYER or PTTA_META_2LAYERS (optionally | PTTA_NLSPN_LEGACY_OFFSET), dtype
  * PTTA_DTYPE_F32, any height and width >= 16 (sizes that are not multiples of 16 follow the reference's ceil-halving encoder
  * maps and decoder crops, nlspnmodel_adapt.py:474-490).  Differences from the MSG_CHN handle: embeddings are (rows, 1024)
  * with rows = n*(H/16)*(W/16); ptta_adapted_count() is 88 (conv1_rgb_meta + every BatchNorm2d weight/bias, in the
@@ -43,10 +43,15 @@ typedef void* ptta_stream;              /* hipStream_t */
  * ptta_backward ignores its two output pointers (read the 88 gradients with ptta_get_grad) and ptta_adam_step takes
  * NULL gradients (it uses the internal ones); after ptta_set_graph(h, 1) (or PTTA_GRAPH=1) ptta_step and ptta_forward_eval replay
  * captured hipGraphs from their second call on (default off for these handles: measured no faster than plain launches);
- * ptta_profile returns -38. */
+ * ptta_profile returns -38.
+ * PTTA_META_2LAYERS: conv1_rgb_meta = Res_Conv(48, 256) (nlspnmodel_adapt.py:37-45, :1376-1377: conv 48 -> 256, BatchNorm2d + LeakyReLU,
+ * conv 256 -> 48 with bias, BatchNorm2d, + its input), fp32 or PTTA_DTYPE_MIXED.  ptta_adapted_count() is 93: the block's seven tensors
+ * first, then every other BatchNorm2d; the reference's list has 97 entries because the block's two BatchNorm2d are listed a second time at
+ * its end, and Adam steps them twice per step: ptta_adapted_repeat() is 2 for those four.  Not with PTTA_NLSPN_SYNCBN_ADAPT (-38: that
+ * list's repeat structure differs). */
 /* PTTA_BACKBONE_COSTDCNET: ExternalModel_Adapt(model_name='costdcnet') -- src/costdcnet_model_adapt.py:31-114 ->
  * CostDCNet._rgbd_meta_contrast (external_src/costdcnet/CostDCNet_adapt.py:207-256), res = 16 planes, up_scale = 4
- * (src/costdcnet_model_adapt.py:47-52), adapt_parameters('meta_bn') (:357-378).  meta_mode PTTA_META_1LAYER, dtype
+ * (src/costdcnet_model_adapt.py:47-52), adapt_parameters('meta_bn') (:357-378).  meta_mode PTTA_META_1LAYER or PTTA_META_2LAYERS, dtype
  * PTTA_DTYPE_F32, hp.max_predict_depth > 0 (the far plane).  Shapes not divisible by 16 run the reference's dual-corner
  * padding (:134-210).  Embeddings are (rows, 512) with rows = n'*(H'/32)*(W'/32) over the padded batch / size;
  * ptta_adapted_count() is 32 (conv1_rgb_meta + every BatchNorm2d weight/bias of Encoder2D, the reference's order);
@@ -59,7 +64,10 @@ typedef void* ptta_stream;              /* hipStream_t */
  * statistics (batch statistics in train AND eval mode; ptta_load_weights ignores every running_* key).  ptta_adapted_count() is 112
  * unique tensors in the reference's order; the reference's list has 116 entries because enc2d.layer{2,3}.0.norm3.{weight,bias} sit
  * behind two SyncBatchNorm modules (norm3 and downsample[1]) and are listed -- and updated by Adam -- twice per step:
- * ptta_adapted_repeat() is 2 for them, 0 for proj.1 / pred.1 (listed, never given a gradient), 1 otherwise. */
+ * ptta_adapted_repeat() is 2 for them, 0 for proj.1 / pred.1 (listed, never given a gradient), 1 otherwise.
+ * PTTA_META_2LAYERS: conv1_rgb_meta = Res_Conv(16, 64) (CostDCNet_adapt.py:555-563, :501-502), fp32 only (PTTA_DTYPE_MIXED stays -38 as for
+ * the 1layer conv).  ptta_adapted_count() is 37, the reference's list 41 entries: the block's two BatchNorm2d come a second time at its
+ * end (ptta_adapted_repeat() 2).  Not with PTTA_SYNCBN_ADAPT (-38). */
 enum { PTTA_BACKBONE_MSG_CHN = 0, PTTA_BACKBONE_NLSPN = 1, PTTA_BACKBONE_COSTDCNET = 2 };
 /* Storage / arithmetic of the MSG_CHN step.
  * PTTA_DTYPE_F32: every 32-channel map fp32, every product fp32-faithful on the bf16 matrix cores (bf16x3 split, fp32 accumulate).
@@ -81,7 +89,7 @@ enum { PTTA_DTYPE_F32 = 0, PTTA_DTYPE_MIXED = 1,
        PTTA_MIXED_KEEP_PROXY = 0x100, PTTA_MIXED_KEEP_BACKWARD = 0x200, PTTA_MIXED_KEEP_HEADS = 0x400,
        /* generic engine, comparison only: the data gradients on bf16-ROUNDED weights, one MFMA per product (round 5's mixed mode) */
        PTTA_MIXED_BWD_ROUNDED_W = 0x800 };
-enum { PTTA_META_1LAYER = 0, PTTA_META_2LAYERS = 1 };   /* conv1_rgb_meta = Conv2d(32,32,3) | Res_Conv(32,128) */
+enum { PTTA_META_1LAYER = 0, PTTA_META_2LAYERS = 1 };   /* conv1_rgb_meta = Conv2d(32,32,3) | Res_Conv(32,128) (NLSPN: 48 / 256, CostDCNet: 16 / 64) */
 /* NLSPN only, OR-ed into meta_mode: ExternalModel_Adapt(..., offset=True) -> args.legacy (src/nlspn_model_adapt.py:62):
  * the confidence gathers add each tap's own (dy, dx) to the learned offset (nlspnmodel_adapt.py:297-302).
  * src/tta_main.py:309-317 always constructs the model this way. */
@@ -167,7 +175,8 @@ int ptta_set_grad(ptta_handle h, const char* name, const float* src, int64_t num
 int ptta_adapted_count(ptta_handle h);
 const char* ptta_adapted_name(ptta_handle h, int index, int64_t* numel_host);
 /* How many times the reference's parameter list names this tensor = the Adam updates it receives per optimizer.step()
- * (torch.optim.Adam walks the list; a tensor listed twice is stepped twice with the same gradient).  1 except under PTTA_SYNCBN_ADAPT. */
+ * (torch.optim.Adam walks the list; a tensor listed twice is stepped twice with the same gradient).  1 except under PTTA_SYNCBN_ADAPT and
+ * under PTTA_META_2LAYERS on NLSPN / CostDCNet (see those backbones). */
 int ptta_adapted_repeat(ptta_handle h, int index);
 
 /* ptta_step for a STREAM of frames (MSG_CHN handles; others forward to ptta_step): besides the step on (image, sparse) it starts, on a stream

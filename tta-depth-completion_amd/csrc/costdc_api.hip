@@ -2,6 +2,8 @@
 // CostDCNet._rgbd_meta_contrast (external_src/costdcnet/CostDCNet_adapt.py:207-256 = CD) behind
 // CostDCNetModel_Adapt (src/costdcnet_model_adapt.py = AD: dual-corner padding :134-210, adapt_parameters('meta_bn')
 // :357-378 -> conv1_rgb_meta + every BatchNorm2d gamma/beta of Encoder2D = 32 tensors / 5,200 values).
+// 2layers (prepare_mode 'meta_selfsup_seq_2layers_ema'): conv1_rgb_meta is Res_Conv(16, 64) (CostDCNet_adapt.py:555-563, :501-502), conv
+// 16 -> 64 - BN - ReLU - conv 64 -> 16 (+ bias) - BN, + its input: 37 tensors, the block's two BatchNorm2d listed twice (41 entries).
 //
 // Program on the generic layer-graph engine (gnet.h):
 //   Encoder2D (models/encoder2d.py:53-102) on cat(image, sparse): conv-BN-ReLU, six ResBlocks (relu(x + relu(bn(conv)))),
@@ -40,6 +42,7 @@ struct costdc_engine : GNet {
     // the adapted set of the reference's DDP run (PTTA_SYNCBN_ADAPT): convert_syncbn() runs before adapt_parameters('meta_bn')
     // (src/tta_main.py:326,339), so every BatchNorm of the model is adapted and has lost its running statistics (AD:364-372)
     int sync_adapt = 0;
+    int meta2 = 0;                                    // the 2layers meta block instead of the 1layer conv
     std::map<std::string, std::pair<int, int>> sbn_ad;
     float* sgrad[4] = {nullptr, nullptr, nullptr, nullptr};
     float* sp_bw = nullptr;
@@ -80,7 +83,19 @@ struct costdc_engine : GNet {
         h4 = H / 4; w4 = W / 4;
         // adapt_parameters('meta_bn') order: parameters with 'meta' in the name first (AD:358-364), then BatchNorm2d affine
         // parameters in module order (AD:365-378)
-        const int ad_mw = add_adapted("conv1_rgb_meta.weight", 16L * 16 * 9), ad_mb = add_adapted("conv1_rgb_meta.bias", 16);
+        const std::string MP = "conv1_rgb_meta.conv1_meta";
+        int ad_mw = -1, ad_mb = -1, ad_w1 = -1;
+        if (!meta2) {
+            ad_mw = add_adapted("conv1_rgb_meta.weight", 16L * 16 * 9); ad_mb = add_adapted("conv1_rgb_meta.bias", 16);
+        } else {
+            // Res_Conv's seven parameters in named_parameters order; its two BatchNorm2d come again at the end of the BatchNorm pass
+            // (the block is registered last, by _prepare_head): torch.optim.Adam steps those four twice per step()
+            ad_w1 = add_adapted(MP + ".0.0.weight", 64L * 16 * 9);
+            const int g1 = add_adapted(MP + ".0.1.weight", 64), b1 = add_adapted(MP + ".0.1.bias", 64);
+            ad_mw = add_adapted(MP + ".1.weight", 16L * 64 * 9); ad_mb = add_adapted(MP + ".1.bias", 16);
+            const int g2 = add_adapted(MP + ".2.weight", 16), b2 = add_adapted(MP + ".2.bias", 16);
+            for (int k : {g1, b1, g2, b2}) adapted[k].rep = 2;
+        }
         t_in = tensor("in2d", N2, H, W, naive ? 4 : 16, false);       // zero-padded to 16 channels for the matrix-core kernel
         const int c1r = tensor("enc2d.c1.r", N2, H, W, 64, true), c1 = tensor("enc2d.c1", N2, H, W, 64, true);
         conv("enc2d.conv1", t_in, -1, c1r, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH, false, false);
@@ -115,7 +130,17 @@ struct costdc_engine : GNet {
         const int f16 = tensor("enc2d.out", N2, h4, w4, 16, true);
         conv("enc2d.conv2", cur, -1, f16, 1, 1, 0, GACT_NONE, W_BOTH, W_BOTH);
         t_feat2d = tensor("feat2d", N2, h4, w4, 16, true);
-        { Op& m = conv("conv1_rgb_meta", f16, -1, t_feat2d, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH); m.ad_w = ad_mw; m.ad_b = ad_mb; }
+        if (!meta2) {
+            Op& m = conv("conv1_rgb_meta", f16, -1, t_feat2d, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH); m.ad_w = ad_mw; m.ad_b = ad_mb;
+        } else {
+            // both passes, batch statistics per pass in train and eval mode; enc2d.out receives the data gradient of the first conv and the
+            // residual's (Encoder2D's BatchNorm2d upstream are adapted)
+            const int mh = tensor(MP + ".h", N2, h4, w4, 64, true), ma = tensor(MP + ".a", N2, h4, w4, 64, true), mr = tensor(MP + ".r", N2, h4, w4, 16, true);
+            conv(MP + ".0.0", f16, -1, mh, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH).ad_w = ad_w1;
+            bn(MP + ".0.1", mh, ma, -1, GACT_RELU, W_BOTH);
+            Op& c2 = conv(MP + ".1", ma, -1, mr, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH); c2.ad_w = ad_mw; c2.ad_b = ad_mb;
+            bn(MP + ".2", mr, t_feat2d, f16, GACT_NONE, W_BOTH).res_relu = false;        // conv1_meta(x) + x: no ReLU after the sum
+        }
         if (sync_adapt) {
             // convert_sync_batchnorm makes one new module per visited attribute: ResBlock.norm3 and its alias downsample[1] become two
             // SyncBatchNorm modules sharing one Parameter, which adapt_parameters then lists twice -> two Adam updates per step
@@ -225,7 +250,7 @@ struct costdc_engine : GNet {
         sp_clamp = falloc((size_t)N * P); pred_net = falloc((size_t)N * P); g_net = falloc((size_t)N * P);
         feat3d = falloc((size_t)N * 16 * h4 * w4 * 16); maskw = falloc((size_t)N * 16 * h4 * w4);
         build_sparse();
-        alloc_common((long)N * h4 * w4, 16, 16);
+        alloc_common((long)N * h4 * w4, 16, meta2 ? 64 : 16);      // weight-gradient partials of the widest adapted conv
     }
 
     // ---- sparse 3-D encoder (models/encoder3d.py) ---------------------------------------------------------------------------
@@ -406,8 +431,8 @@ struct costdc_engine : GNet {
         }
         // ResBlock.norm3 is registered a second time inside `downsample` (same tensors): the norm3 keys are authoritative
         if (name.rfind("enc2d.", 0) == 0 && name.find(".downsample.1.") != std::string::npos) return 0;
-        // BatchNorm2d running statistics are dropped by adapt_parameters('meta_bn') (AD:370-372)
-        if (name.rfind("enc2d.", 0) == 0 && (ends("running_mean") || ends("running_var") || ends("num_batches_tracked"))) return 0;
+        // BatchNorm2d running statistics are dropped by adapt_parameters('meta_bn') (AD:370-372) -- Encoder2D's and the 2layers block's
+        if ((name.rfind("enc2d.", 0) == 0 || (meta2 && name.rfind("conv1_rgb_meta.", 0) == 0)) && (ends("running_mean") || ends("running_var") || ends("num_batches_tracked"))) return 0;
         if (ends("running_mean") || ends("running_var") || ends("num_batches_tracked")) {
             if (sync_adapt) return 0;
             for (Op& o : ops)
@@ -496,6 +521,7 @@ GNet* costdc_create(int n, int h, int w, const ptta_hparams* hp, float max_depth
     // launches on this engine (the host keeps ahead of the GPU either way: DESIGN_LOG.md section 9) -> opt-in: ptta_set_option(h, "graph", 1) / PTTA_GRAPH=1
     e->use_graph = env.graph == 1 ? 1 : 0;
     e->sync_adapt = (flags & 1) ? 1 : 0;
+    e->meta2 = (flags & 2) ? 1 : 0;
     e->build();
     if (e->oom || !e->step_dev) { delete e; *rc = -12; return nullptr; }
     if (e->upload_hparams(nullptr)) { delete e; *rc = -5; return nullptr; }

@@ -258,7 +258,7 @@ __global__ void gbn_apply_kernel(GView x, GView res, GView y, int npass, int act
 // statistics pass
 int ptta_launch_gbn_forward(const GView& x, const GView& res, const GView& y, int npass, int act, float eps, const float* gamma,
                             const float* beta, float* part, float* st, hipStream_t s, int fused_blocks, int act_first, const PttaStatSync* sync,
-                            float* rm, float* rv, long long* nbt, float momentum, int repeats, float* st_eval) {
+                            float* rm, float* rv, long long* nbt, float momentum, int repeats, float* st_eval, int res_relu) {
     const int C = x.C, CT = C < 256 ? C : 256, nsub = 256 / CT;
     const size_t lds = (size_t)nsub * 2 * CT * sizeof(float);
     const long R = (long)(x.B / npass) * x.H * x.W;
@@ -272,7 +272,7 @@ int ptta_launch_gbn_forward(const GView& x, const GView& res, const GView& y, in
     if ((C & 3) || (x.ld & 3) || (y.ld & 3) || (res.p && (res.ld & 3))) return -22;
     const long total = (long)x.B * x.H * x.W * (C >> 2);
     long ab = (total + 255) / 256; if (ab > 16384) ab = 16384; if (ab < 1) ab = 1;
-    hipLaunchKernelGGL(gbn_apply_kernel, dim3((int)ab), dim3(256), 0, s, x, res, y, npass, act, st, 1, act_first);
+    hipLaunchKernelGGL(gbn_apply_kernel, dim3((int)ab), dim3(256), 0, s, x, res, y, npass, act, st, res_relu, act_first);
     PTTA_CHECK_LAUNCH();
     return 0;
 }

@@ -86,6 +86,7 @@ struct Op {
     bool first_raw = true, first_res = true;
     bool tracked = false;             // running statistics kept: updated in train mode (momentum 0.1), used in eval mode
     bool act_first = false;           // with a residual: y = relu(act(bn(x)) + res) instead of relu(bn(x) + res)
+    bool res_relu = true;             // with a residual: false = y = act(bn(x)) + res without the final ReLU (Res_Conv of the 2layers meta block)
     int stat_repeats = 1;             // the reference runs this layer `repeats` times per training forward on the same input
     float *rm = nullptr, *rv = nullptr; long long* nbt = nullptr;
     float *rm_own = nullptr, *rv_own = nullptr;   // BatchNorm2d (not tracked): the LOADED running statistics, used by the stage-2 head trainer only

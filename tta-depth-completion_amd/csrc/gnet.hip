@@ -125,7 +125,7 @@ int GNet::run_bn_fwd(const Op& o, bool train, hipStream_t s) {
         if (!o.has_running) return fail("running statistics of " + o.bname + " not loaded (the stage-2 head trainer evaluates BatchNorm2d from them)", -3);
         if (ptta_launch_gbn_eval_affine(bn_gamma(o), bn_beta(o), o.rm_own, o.rv_own, BN_EPS, x.C, o.st_eval, s)) return fail("batch-norm " + o.bname + " (prepare) launch failed", -5);
         o.st_eval_valid = false;
-        if (ptta_launch_gbn_apply(x, res, y, 1, o.act, o.st_eval, 1, s, o.act_first ? 1 : 0)) return fail("batch-norm " + o.bname + " (prepare) launch failed", -5);
+        if (ptta_launch_gbn_apply(x, res, y, 1, o.act, o.st_eval, o.res_relu ? 1 : 0, s, o.act_first ? 1 : 0)) return fail("batch-norm " + o.bname + " (prepare) launch failed", -5);
         return 0;
     }
     if (o.tracked && !train) {                              // eval mode: running statistics
@@ -135,7 +135,7 @@ int GNet::run_bn_fwd(const Op& o, bool train, hipStream_t s) {
             if (ptta_launch_gbn_eval_affine(bn_gamma(o), bn_beta(o), o.rm, o.rv, BN_EPS, x.C, o.st_eval, s)) return fail("batch-norm " + o.bname + " (eval) launch failed", -5);
             o.st_eval_valid = true;
         }
-        if (ptta_launch_gbn_apply(x, res, y, 1, o.act, o.st_eval, 1, s, o.act_first ? 1 : 0))
+        if (ptta_launch_gbn_apply(x, res, y, 1, o.act, o.st_eval, o.res_relu ? 1 : 0, s, o.act_first ? 1 : 0))
             return fail("batch-norm " + o.bname + " (eval) launch failed", -5);
         return 0;
     }
@@ -143,7 +143,8 @@ int GNet::run_bn_fwd(const Op& o, bool train, hipStream_t s) {
     const int fused = o.fused_from >= 0 ? ptta_gconv_x3_tiles(xt.B / npass, xt.H, xt.W) : 0;
     const bool upd = o.tracked && train && o.rm && o.rv;      // running statistics + eval affine out of the finalize launch
     if (ptta_launch_gbn_forward(x, res, y, npass, o.act, BN_EPS, bn_gamma(o), bn_beta(o), fused ? o.part : bn_part, o.st, s, fused, o.act_first ? 1 : 0, &stat_sync,
-                                upd ? o.rm : nullptr, upd ? o.rv : nullptr, upd ? o.nbt : nullptr, 0.1f, o.stat_repeats, upd ? o.st_eval : nullptr))
+                                upd ? o.rm : nullptr, upd ? o.rv : nullptr, upd ? o.nbt : nullptr, 0.1f, o.stat_repeats, upd ? o.st_eval : nullptr,
+                                o.res_relu ? 1 : 0))
         return fail("batch-norm " + o.bname + " launch failed", -5);
     if (upd) o.st_eval_valid = true;
     return 0;
@@ -215,7 +216,7 @@ int GNet::run_bn_bwd(const Op& o, hipStream_t s) {
     const int npass = o.xw[0] == W_BOTH ? 2 : 1;
     float* dg = o.ad_g >= 0 ? gall + adapted[o.ad_g].goff : nullptr;
     float* db = o.ad_beta >= 0 ? gall + adapted[o.ad_beta].goff : nullptr;
-    if (ptta_launch_gbn_backward(x, g, y, gx, gres, npass, o.act, o.res >= 0 ? 1 : 0, o.first_raw ? 0 : 1, o.first_res ? 0 : 1,
+    if (ptta_launch_gbn_backward(x, g, y, gx, gres, npass, o.act, (o.res >= 0 && o.res_relu) ? 1 : 0, o.first_raw ? 0 : 1, o.first_res ? 0 : 1,
                                  bn_gamma(o), o.st, bn_part, bn_bw, dg, db, s, o.act_first ? 1 : 0, &stat_sync))
         return fail("batch-norm gradient of " + o.bname + " failed", -5);
     return 0;

@@ -2,6 +2,8 @@
 // NLSPNModel_Adapt._rgbd_meta_contrast (external_src/NLSPN/src/model/nlspnmodel_adapt.py:850-944) with
 // adapt_parameters('meta_bn') (src/nlspn_model_adapt.py:322-337): conv1_rgb_meta + every BatchNorm2d gamma/beta
 // adapt (88 tensors / 40,048 values), every BatchNorm2d normalises with batch statistics in train and eval mode.
+// 2layers (prepare_mode 'meta_selfsup_seq_2layers_ema'): conv1_rgb_meta is Res_Conv(48, 256) (nlspnmodel_adapt.py:37-45, :1376-1377),
+// conv 48 -> 256 - BN - LeakyReLU(0.2) - conv 256 -> 48 (+ bias) - BN, + its input: 93 tensors, the block's two BatchNorm2d listed twice (97 entries).
 //
 // The network is a flat op list built once per handle ("program"): CONV (one or two channel-concatenated
 // sources, so torch.cat never materialises), BN (+activation, + residual add of a BasicBlock), then the fused
@@ -64,7 +66,7 @@ struct nlspn_engine : GNet {
     int t_sd16 = -1;
     int t_img = -1, t_sd = -1, t_pred = -1, t_oa = -1, t_conf = -1, t_fe6 = -1;
     float *off9 = nullptr, *aff9 = nullptr, *goff9 = nullptr, *gaff9 = nullptr, *feats = nullptr, *gy = nullptr, *gping = nullptr;
-    int legacy = 0, heads_adapted = 0;
+    int legacy = 0, heads_adapted = 0, meta2 = 0;
     int enc_ops_end = 0;               // ops [0, enc_ops_end) = conv1 .. conv6: what the stage-2 head trainer runs of the backbone
 
     static int half(int v) { return (v + 1) / 2; }                 // 3x3 stride 2 padding 1: ceil
@@ -77,7 +79,19 @@ struct nlspn_engine : GNet {
         const int H2 = half(H), W2 = half(W), H4 = half(H2), W4 = half(W2), H8 = half(H4), W8 = half(W4), H16 = half(H8), W16 = half(W8);
         const int N2 = 2 * N;
         // the adapted meta conv comes first in the reference's parameter list (src/nlspn_model_adapt.py:324-328)
-        const int ad_mw = add_adapted("conv1_rgb_meta.weight", 48L * 48 * 9), ad_mb = add_adapted("conv1_rgb_meta.bias", 48);
+        const std::string MP = "conv1_rgb_meta.conv1_meta";
+        int ad_mw = -1, ad_mb = -1, ad_w1 = -1;
+        if (!meta2) {
+            ad_mw = add_adapted("conv1_rgb_meta.weight", 48L * 48 * 9); ad_mb = add_adapted("conv1_rgb_meta.bias", 48);
+        } else {
+            // Res_Conv's seven parameters in named_parameters order; the BatchNorm pass (:329-337) lists its two BatchNorm2d again after
+            // every other one (the block is registered last, by _prepare_head): torch.optim.Adam steps those four twice per step()
+            ad_w1 = add_adapted(MP + ".0.0.weight", 256L * 48 * 9);
+            const int g1 = add_adapted(MP + ".0.1.weight", 256), b1 = add_adapted(MP + ".0.1.bias", 256);
+            ad_mw = add_adapted(MP + ".1.weight", 48L * 256 * 9); ad_mb = add_adapted(MP + ".1.bias", 48);
+            const int g2 = add_adapted(MP + ".2.weight", 48), b2 = add_adapted(MP + ".2.bias", 48);
+            for (int k : {g1, b1, g2, b2}) adapted[k].rep = 2;
+        }
         // the 3-channel image and the 1-channel sparse depth are staged zero-padded to 16 channels so that their first
         // convolutions run on the matrix-core kernel too (weight rows of the padding channels are zero)
         t_img = tensor("image", N2, H, W, naive ? 3 : 16, false);
@@ -87,8 +101,18 @@ struct nlspn_engine : GNet {
         const int fe1 = tensor("fe1", N2, H, W, 64, true);
         const int fe1_rgb = slice("fe1_rgb", fe1, 0, 48), fe1_dep = slice("fe1_dep", fe1, 48, 16);
         conv("conv1_rgb.0", t_img, -1, rgb1, 3, 1, 0, GACT_LRELU, W_BOTH, W_BOTH, false, false);
-        conv("conv1_rgb_meta", rgb1, -1, fe1_rgb, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH);
-        ops.back().ad_w = ad_mw; ops.back().ad_b = ad_mb;
+        if (!meta2) {
+            conv("conv1_rgb_meta", rgb1, -1, fe1_rgb, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH);
+            ops.back().ad_w = ad_mw; ops.back().ad_b = ad_mb;
+        } else {
+            // both passes through the block, batch statistics per pass (also in eval mode: meta_bn drops the running statistics); rgb1
+            // has no gradient buffer (nothing upstream is adapted), so the first conv gets no data gradient and the residual none either
+            const int mh = tensor(MP + ".h", N2, H, W, 256, true), ma = tensor(MP + ".a", N2, H, W, 256, true), mr = tensor(MP + ".r", N2, H, W, 48, true);
+            conv(MP + ".0.0", rgb1, -1, mh, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH).ad_w = ad_w1;
+            bn(MP + ".0.1", mh, ma, -1, GACT_LRELU, W_BOTH);                                 // NLSPN's conv_bn_relu: LeakyReLU(0.2) (common.py:45-56)
+            Op& c2 = conv(MP + ".1", ma, -1, mr, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH); c2.ad_w = ad_mw; c2.ad_b = ad_mb;
+            bn(MP + ".2", mr, fe1_rgb, rgb1, GACT_NONE, W_BOTH).res_relu = false;         // conv1_meta(x) + x: no ReLU after the sum
+        }
         conv("conv1_dep.0", sd16, -1, fe1_dep, 3, 1, 0, GACT_LRELU, W_BOTH, W_BOTH, false, false);
         if (!naive) { convs["conv1_rgb.0"].Ci_real = 3; convs["conv1_dep.0"].Ci_real = 1; t_sd16 = sd16; }
         // ResNet34 stages (nlspnmodel_adapt.py:400-406; BasicBlock :70-116)
@@ -203,7 +227,7 @@ struct nlspn_engine : GNet {
         feats = falloc((size_t)(PROP_TIME + 1) * N * P);
         gy = falloc((size_t)N * P); gping = falloc((size_t)N * P);
         S = falloc(1);
-        alloc_common((long)N * P, 48, 48);
+        alloc_common((long)N * P, 48, meta2 ? 256 : 48);        // weight-gradient partials of the widest adapted conv (48 <-> 256 under 2layers)
     }
 
     // ---- weights that are not convolutions / BatchNorm affine ----------------------------------------------------------
@@ -311,6 +335,7 @@ GNet* nlspn_create(int n, int h, int w, const ptta_hparams* hp, int legacy_offse
     if (n < 1 || h < 16 || w < 16 || !hp) { *rc = -22; return nullptr; }
     nlspn_engine* e = new nlspn_engine();
     e->N = e->Nu = n; e->H = e->Hu = h; e->W = e->Wu = w; e->hp = *hp; e->legacy = (legacy_offset & 1) ? 1 : 0; e->heads_adapted = (legacy_offset & 2) ? 1 : 0;
+    e->meta2 = (legacy_offset & 4) ? 1 : 0;
     const PttaCreateEnv env = ptta_create_env();
     e->naive = env.naive;          // direct fp32 kernels everywhere (validation)
     e->x6 = 0;                     // (third operand plane: off -- matrix-core bound, parity holds without)

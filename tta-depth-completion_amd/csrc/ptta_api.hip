@@ -1586,9 +1586,13 @@ int ptta_create(ptta_handle* out, int backbone_id, int meta_mode, int n, int hei
     const int gmix = (dtype & 0xff) == PTTA_DTYPE_MIXED ? ((((dtype >> 8) & 1) ? 0 : 1) | (((dtype >> 8) & 2) ? 0 : (((dtype >> 8) & 8) ? 2 : 4))) : 0;
     if (backbone_id != PTTA_BACKBONE_MSG_CHN && (dtype & 0xff) == PTTA_DTYPE_MIXED) dtype = PTTA_DTYPE_F32;
     if (backbone_id == PTTA_BACKBONE_NLSPN) {
-        if ((meta_mode & ~(PTTA_NLSPN_LEGACY_OFFSET | PTTA_NLSPN_SYNCBN_ADAPT)) != PTTA_META_1LAYER || dtype != PTTA_DTYPE_F32) return -38;
+        // 2layers: the Res_Conv(48, 256) block (nlspn_api.hip), fp32 and mixed; not with the adapted set of the DDP run (its repeat structure differs)
+        const int meta = meta_mode & ~(PTTA_NLSPN_LEGACY_OFFSET | PTTA_NLSPN_SYNCBN_ADAPT);
+        if ((meta != PTTA_META_1LAYER && meta != PTTA_META_2LAYERS) || dtype != PTTA_DTYPE_F32) return -38;
+        if (meta == PTTA_META_2LAYERS && (meta_mode & PTTA_NLSPN_SYNCBN_ADAPT)) return -38;
         int rc = 0;
-        GNet* e = nlspn_create(n, height, width, hp, ((meta_mode & PTTA_NLSPN_LEGACY_OFFSET) ? 1 : 0) | ((meta_mode & PTTA_NLSPN_SYNCBN_ADAPT) ? 2 : 0), &rc);
+        GNet* e = nlspn_create(n, height, width, hp, ((meta_mode & PTTA_NLSPN_LEGACY_OFFSET) ? 1 : 0) | ((meta_mode & PTTA_NLSPN_SYNCBN_ADAPT) ? 2 : 0) |
+                               (meta == PTTA_META_2LAYERS ? 4 : 0), &rc);
         if (!e) return rc ? rc : -12;
         e->mixed = e->naive ? 0 : gmix;
         ptta_ctx* c = new ptta_ctx();
@@ -1600,9 +1604,12 @@ int ptta_create(ptta_handle* out, int backbone_id, int meta_mode, int n, int hei
         // (no mixed mode for CostDCNet: with single-MFMA data gradients its scored depth leaves the tolerance -- 2.0e-3 / 1.7e-3 at 480x640 /
         // 320x400, with hi + lo weights in them still 1.1e-3 / 1.2e-3, with single-MFMA proxy frames alone 8.9e-4 at 320x400, for 2 - 3 % of
         // the step: profiles/r06_nlspn_costdcnet_mixed.txt -- its argmax over the cost volume amplifies any change of the update)
-        if ((meta_mode & ~PTTA_SYNCBN_ADAPT) != PTTA_META_1LAYER || dtype != PTTA_DTYPE_F32 || !hp || gmix) return -38;
+        // 2layers: the Res_Conv(16, 64) block (costdc_api.hip), fp32 only, not with PTTA_SYNCBN_ADAPT
+        const int meta = meta_mode & ~PTTA_SYNCBN_ADAPT;
+        if ((meta != PTTA_META_1LAYER && meta != PTTA_META_2LAYERS) || dtype != PTTA_DTYPE_F32 || !hp || gmix) return -38;
+        if (meta == PTTA_META_2LAYERS && (meta_mode & PTTA_SYNCBN_ADAPT)) return -38;
         int rc = 0;
-        GNet* e = costdc_create(n, height, width, hp, hp->max_predict_depth, (meta_mode & PTTA_SYNCBN_ADAPT) ? 1 : 0, &rc);
+        GNet* e = costdc_create(n, height, width, hp, hp->max_predict_depth, ((meta_mode & PTTA_SYNCBN_ADAPT) ? 1 : 0) | (meta == PTTA_META_2LAYERS ? 2 : 0), &rc);
         if (!e) return rc ? rc : -12;
         e->mixed = e->naive ? 0 : gmix;
         ptta_ctx* c = new ptta_ctx();

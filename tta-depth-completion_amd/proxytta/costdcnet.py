@@ -26,14 +26,16 @@ def costdcnet_adapted_names(keys, syncbn=False):
     BatchNorm is a SyncBatchNorm by then and passes the isinstance test (:364-366): Encoder2D's, the BatchNorm1d inside each
     MinkowskiBatchNorm (`enc3d.<layer>.bn`), UNet3D's BatchNorm3d and the heads' BatchNorm1d -- 116 entries.
     convert_sync_batchnorm builds one new module per visited attribute, so ResBlock.norm3 and its alias downsample[1] are two
-    modules around ONE Parameter: enc2d.layer{2,3}.0.norm3.{weight,bias} are listed twice (and stepped twice by Adam)."""
-    names = [k for k in keys if 'meta' in k]
+    modules around ONE Parameter: enc2d.layer{2,3}.0.norm3.{weight,bias} are listed twice (and stepped twice by Adam).
+    2layers: the Res_Conv block's seven parameters come first, its two BatchNorm2d again at the end of the BatchNorm pass (the block is
+    registered last): 37 tensors, 41 entries."""
+    names = [k for k in keys if 'meta' in k and not k.endswith(_BUFFERS)]
     for k in keys:
         if not k.endswith('.running_mean'):
             continue
         pre = k[:-len('.running_mean')]
         if not syncbn:
-            if k.startswith('enc2d.') and '.downsample.1.' not in k:
+            if (k.startswith('enc2d.') and '.downsample.1.' not in k) or k.startswith('conv1_rgb_meta.'):
                 names += [pre + '.weight', pre + '.bias']
             continue
         if pre.startswith('enc2d.'):
@@ -82,10 +84,11 @@ class CostDCNetModel_Adapt(MsgChnModel_Adapt):
 
     def _prepare_head(self, mode=''):
         """CostDCNet._prepare_head (CostDCNet_adapt.py:426-496)."""
-        if 'meta' not in mode or 'selfsup' not in mode or 'ema' not in mode or 'seq' not in mode or '1layer' not in mode:
-            raise NotImplementedError('hot path covers prepare_mode meta_selfsup_seq_1layer_ema, got %r' % mode)
+        if 'meta' not in mode or 'selfsup' not in mode or 'ema' not in mode or 'seq' not in mode or \
+                ('1layer' not in mode and '2layers' not in mode):
+            raise NotImplementedError('hot path covers prepare_mode meta_selfsup_seq_{1layer,2layers}_ema, got %r' % mode)
         self.prepare_mode = mode
-        self.meta = '1layer'
+        self.meta = '2layers' if '2layers' in mode else '1layer'
         for k, s in synth.costdcnet_keys(mode):
             if k.startswith(('proj', 'pred', 'conv1_rgb_meta')):
                 self.model._leaf(k, _init_tensor(k, s).to(self.device), not k.endswith(_BUFFERS))
@@ -142,7 +145,7 @@ class CostDCNetModel_Adapt(MsgChnModel_Adapt):
             if self.prepare_mode is None:
                 raise RuntimeError('_prepare_head(mode) must be called before forward (tta_main.py:322)')
             eng = Engine(n, h, w, backbone='costdcnet', max_input_depth=self.max_input_depth, max_predict_depth=self.max_depth,
-                         syncbn_adapted=self.sync_bn, **self.hparams)
+                         syncbn_adapted=self.sync_bn, meta=self.meta, **self.hparams)
             assert all(self.adapted_listed.count(k) == max(eng.adapted_repeat[k], 1) for k in eng.adapted), 'listing counts drifted'
             assert eng.adapted == self.adapted, 'adapted parameter list drifted from the library'
             eng.load_state_dict(self.model.state_dict())      # running statistics are bound by pointer and updated in place

@@ -83,8 +83,8 @@ class Engine:
                                   self.n, self.h, self.w, code, byref(self.hp))
         if rc != 0:
             why = {-19: 'no HIP device', -12: 'out of device memory', -22: 'invalid size / argument',
-                   -38: 'configuration not on the accelerated path (NLSPN needs fp32 and '
-                        'the 1layer meta conv; MSG_CHN needs the 1layer or 2layers meta layer)'}.get(rc, 'see include/ptta.h')
+                   -38: 'configuration not on the accelerated path (every backbone runs the 1layer and the 2layers meta layer; '
+                        'CostDCNet in fp32 only; the 2layers block not with the SyncBN-adapted set of NLSPN / CostDCNet)'}.get(rc, 'see include/ptta.h')
             raise RuntimeError('ptta_create failed (%d): %s' % (rc, why))
         for k, v in (options or {}).items():       # include/ptta.h ptta_set_option
             self.set_option(k, v)

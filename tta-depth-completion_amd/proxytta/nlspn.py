@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from . import synth
 from .engine import Engine
+from .costdcnet import _unique
 from .model import MsgChnModel_Adapt, _ForwardFn, _init_tensor, _Tree
 
 _BUFFERS = ('running_mean', 'running_var', 'num_batches_tracked')
@@ -25,8 +26,10 @@ def nlspn_adapted_names(keys, syncbn=False):
     """adapt_parameters('meta_bn') (src/nlspn_model_adapt.py:322-337): parameters whose name contains 'meta', then
     weight / bias of every BatchNorm2d in module order (the heads' BatchNorm1d are not BatchNorm2d).  After
     convert_syncbn() (src/tta_main.py:326 runs it BEFORE adapt_parameters) every BatchNorm is a SyncBatchNorm and the
-    isinstance test also matches the heads': proj.1, proj_t.1, pred.1 join the list (94 tensors)."""
-    names = [k for k in keys if 'meta' in k]
+    isinstance test also matches the heads': proj.1, proj_t.1, pred.1 join the list (94 tensors).
+    2layers: the Res_Conv block's seven parameters come first; its two BatchNorm2d are BatchNorm2d too, so their gamma / beta are
+    listed a second time, where the block sits in module order (last): 93 tensors, 97 entries."""
+    names = [k for k in keys if 'meta' in k and not k.endswith(_BUFFERS)]
     for k in keys:
         if k.endswith('.running_mean') and (syncbn or not k.startswith(('proj', 'pred'))):
             pre = k[:-len('.running_mean')]
@@ -78,27 +81,34 @@ class NlspnModel_Adapt(MsgChnModel_Adapt):
 
     def _prepare_head(self, mode=''):
         """NLSPNModel_Adapt._prepare_head (nlspnmodel_adapt.py:1333-1396)."""
-        if 'meta' not in mode or 'selfsup' not in mode or 'ema' not in mode or 'seq' not in mode or '1layer' not in mode:
-            raise NotImplementedError('hot path covers prepare_mode meta_selfsup_seq_1layer_ema, got %r' % mode)
+        if 'meta' not in mode or 'selfsup' not in mode or 'ema' not in mode or 'seq' not in mode or \
+                ('1layer' not in mode and '2layers' not in mode):
+            raise NotImplementedError('hot path covers prepare_mode meta_selfsup_seq_{1layer,2layers}_ema, got %r' % mode)
         self.prepare_mode = mode
-        self.meta = '1layer'
+        self.meta = '2layers' if '2layers' in mode else '1layer'
         for k, s in synth.nlspn_keys(mode):
             if k.startswith(('proj', 'pred', 'conv1_rgb_meta')):
                 self.model._leaf(k, _init_tensor(k, s).to(self.device), not k.endswith(_BUFFERS))
-        self.adapted = nlspn_adapted_names([k for k, _ in synth.nlspn_keys(mode)], self.sync_bn)
+        self._set_adapted()
+
+    def _set_adapted(self):
+        # adapted_listed: the reference's parameter list (2layers names the block's BatchNorm2d twice); adapted: the tensors behind it
+        self.adapted_listed = nlspn_adapted_names([k for k, _ in synth.nlspn_keys(self.prepare_mode)], self.sync_bn)
+        self.adapted = _unique(self.adapted_listed)
         self._clear_engines()
 
     def convert_syncbn(self, apex=False):
         super().convert_syncbn(apex)
         if self.prepare_mode is not None:           # heads exist: the adapted list grows to the 94 tensors of the DDP run
-            self.adapted = nlspn_adapted_names([k for k, _ in synth.nlspn_keys(self.prepare_mode)], True)
-            self._clear_engines()
+            self._set_adapted()
 
     def adapt_parameters(self, mode=None):
         if mode != 'meta_bn':
             raise NotImplementedError("adapt_mode %r: only 'meta_bn' (the NLSPN scripts' mode) is on the accelerated path" % mode)
         params = dict(self.model.named_parameters())
-        return nn.ParameterList([params[k] for k in self.adapted])
+        # 2layers: four tensors listed twice -- torch.optim.Adam steps them twice per step(), as the reference's (torch 1.10.1; with torch >= 2.0
+        # on the GPU build the optimizer with foreach=False for the same), and the fused step() does the same on device
+        return nn.ParameterList([params[k] for k in self.adapted_listed])
 
     def _engine(self, image):
         n, _, h, w = image.shape
@@ -108,7 +118,8 @@ class NlspnModel_Adapt(MsgChnModel_Adapt):
             if self.prepare_mode is None:
                 raise RuntimeError('_prepare_head(mode) must be called before forward (tta_main.py:322)')
             eng = Engine(n, h, w, backbone='nlspn', legacy_offset=self.legacy, max_input_depth=self.max_input_depth,
-                         syncbn_adapted=self.sync_bn, **self.hparams)
+                         syncbn_adapted=self.sync_bn, meta=self.meta, **self.hparams)
+            assert all(self.adapted_listed.count(k) == max(eng.adapted_repeat[k], 1) for k in eng.adapted), 'listing counts drifted'
             assert eng.adapted == self.adapted, 'adapted parameter list drifted from the library'
             eng.load_state_dict(self.model.state_dict())     # the heads' BatchNorm1d buffers are bound and updated in place
             params = dict(self.model.named_parameters())

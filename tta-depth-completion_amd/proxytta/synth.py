@@ -6,7 +6,8 @@ committed and no torch RNG (CPU and GPU generators differ) is involved.
 
 The key/shape table mirrors the state_dict of the reference network after
 ``_prepare_head('meta_selfsup_seq_{1layer,2layers}_ema')``
-(external_src/MSG_CHN/workspace/exp_msg_chn/network_exp_msg_chn_adapt.py:314-336, :1022-1087).
+(external_src/MSG_CHN/workspace/exp_msg_chn/network_exp_msg_chn_adapt.py:314-336, :1022-1087), and of the NLSPN /
+CostDCNet networks after the same call (Res_Conv(48, 256) / Res_Conv(16, 64) as the 2layers block).
 """
 import zlib
 
@@ -39,6 +40,22 @@ def _mlp_keys(prefix, din, dh, dout):
             (prefix + '.1.running_mean', (dh,)), (prefix + '.1.running_var', (dh,)),
             (prefix + '.1.num_batches_tracked', ()),
             (prefix + '.3.weight', (dout, dh)), (prefix + '.3.bias', (dout,))]
+
+
+def _res_conv_keys(ch_in, ch_hidden):
+    """state_dict of Res_Conv(ch_in, ch_hidden, 3, 1, 1) as conv1_rgb_meta, the 2layers meta block of every backbone:
+    conv_bn_relu (3x3 conv without bias, BatchNorm2d, ReLU), Conv2d(ch_hidden, ch_in, 3) with bias, BatchNorm2d(ch_in)."""
+    p = 'conv1_rgb_meta.conv1_meta'
+    return [(p + '.0.0.weight', (ch_hidden, ch_in, 3, 3))] + _bn_keys(p + '.0.1', ch_hidden) + \
+        [(p + '.1.weight', (ch_in, ch_hidden, 3, 3)), (p + '.1.bias', (ch_in,))] + _bn_keys(p + '.2', ch_in)
+
+
+def _meta_keys(prepare_mode, ch_in, ch_hidden, backbone):
+    if '2layers' in prepare_mode:
+        return _res_conv_keys(ch_in, ch_hidden)
+    if '1layer' not in prepare_mode:
+        raise NotImplementedError('%s key table covers the 1layer and 2layers meta layers only' % backbone)
+    return [('conv1_rgb_meta.weight', (ch_in, ch_in, 3, 3)), ('conv1_rgb_meta.bias', (ch_in,))]
 
 
 def msg_chn_keys(prepare_mode='meta_selfsup_seq_1layer_ema'):
@@ -85,8 +102,7 @@ def nlspn_keys(prepare_mode='meta_selfsup_seq_1layer_ema'):
     (external_src/NLSPN/src/model/nlspnmodel_adapt.py:376-452) with the ResNet34 stages [3,4,6,3] of
     BasicBlocks (:70-116), the propagation layer (:189-253) and the heads / meta layer of
     _prepare_head (:1333-1376)."""
-    if '1layer' not in prepare_mode:
-        raise NotImplementedError('NLSPN key table covers the canonical 1layer meta layer only')
+    meta = _meta_keys(prepare_mode, 48, 256, 'NLSPN')
     keys = [('conv1_rgb.0.weight', (48, 3, 3, 3)), ('conv1_rgb.0.bias', (48,)),
             ('conv1_dep.0.weight', (16, 1, 3, 3)), ('conv1_dep.0.bias', (16,))]
     inpl = 64
@@ -113,8 +129,7 @@ def nlspn_keys(prepare_mode='meta_selfsup_seq_1layer_ema'):
     keys += _mlp_keys('proj', 512, 1024, 1024)
     keys += _mlp_keys('proj_t', 512, 1024, 1024)
     keys += _mlp_keys('pred', 1024, 1024, 1024)
-    keys += [('conv1_rgb_meta.weight', (48, 48, 3, 3)), ('conv1_rgb_meta.bias', (48,))]
-    return keys
+    return keys + meta
 
 
 def formula_state_dict_nlspn(prepare_mode='meta_selfsup_seq_1layer_ema', gain=1.0):
@@ -199,8 +214,7 @@ def costdcnet_keys(prepare_mode='meta_selfsup_seq_1layer_ema'):
     """Ordered (name, shape) list of the CostDCNet TTA network's state_dict: CostDCNet.__init__
     (external_src/costdcnet/CostDCNet_adapt.py:13-23: Encoder2D(4,16), Encoder3D(1,16,planes=(32,48,64)),
     UNet3D(32,16,f_maps=[32,48,64,80])) plus the heads / meta layer of _prepare_head (:426-496, 'selfsup'+'ema'+'1layer')."""
-    if '1layer' not in prepare_mode:
-        raise NotImplementedError('CostDCNet key table covers the canonical 1layer meta layer only')
+    meta = _meta_keys(prepare_mode, 16, 64, 'CostDCNet')
     keys = [('enc2d.conv1.weight', (64, 4, 3, 3)), ('enc2d.conv1.bias', (64,))] + _bn_keys('enc2d.norm1', 64)
     inpl = 64
     for li, (planes, stride) in enumerate([(64, 1), (96, 2), (128, 2)]):
@@ -238,8 +252,7 @@ def costdcnet_keys(prepare_mode='meta_selfsup_seq_1layer_ema'):
         keys += _p3d_keys(pre + '.0', cin, cout) + _p3d_keys(pre + '.1', cout, cout)
     keys += [('unet3d.classif0.weight', (16, 32, 1, 1, 1)), ('unet3d.classif0.bias', (16,))]
     keys += _mlp_keys('proj', 160, 512, 512) + _mlp_keys('proj_t', 160, 512, 512) + _mlp_keys('pred', 512, 512, 512)
-    keys += [('conv1_rgb_meta.weight', (16, 16, 3, 3)), ('conv1_rgb_meta.bias', (16,))]
-    return keys
+    return keys + meta
 
 
 def formula_state_dict_costdcnet(prepare_mode='meta_selfsup_seq_1layer_ema', gain=1.0):
