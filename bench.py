@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — ProxyTTA step throughput on MI355X (metric of BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W [--dtype mixed|fp32]
+  python bench.py --gpus N --steps K --warmup W [--dtype mixed|fp32] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the headline line (metric, value,
+ms_per_step, dtype, config, timing).  --full adds everything else below (roofline, cpu_baseline, the call-by-call, other-dtype and
+other-launch-form legs, from_host_memory, the pipelined-vs-plain replay, other_workloads): all of it after the timed steps, so the
+headline figure is the same with or without it.
 
 One "step" = one pass of the hot path (forward [grad + proxy pass + heads] + loss + backward +
 Adam, src/tta_main.py:610-633) over one synthetic 352x1216 KITTI-shaped frame, MSG_CHN backbone,
@@ -9,7 +14,7 @@ prepare_mode meta_selfsup_seq_1layer_ema, batch 1 per GPU, inputs resident in HB
 N > 1: one process per GPU (torch.distributed.run), independent frame streams sharded over the
 ranks, no data-path collective ("weak" scaling); barrier + max-over-ranks timing.
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  Extra objects (roofline and cpu_baseline with --full only):
   roofline     dominant kernel class = the stride-1 3x3 32->32 convolutions with ReLU on load
                (conv32_s1_x3_kernel<true, ...> on large maps + conv32_s1_small_kernel<true, ...>):
                algorithmic bytes/MACs of its launches (SURVEY.md §8d counting rule: input + output +
@@ -853,12 +858,17 @@ def main():
     ap.add_argument('--dtype', default=os.environ.get('PTTA_BENCH_DTYPE', 'mixed'), choices=['fp32', 'mixed'],
                     help="'mixed' (default): BASELINE config 2 -- the scored depth's tensors fp32 / bf16x3, the no_grad proxy pass, the heads and the "
                          "data gradients bf16 / single MFMA (include/ptta.h PTTA_DTYPE_MIXED); 'fp32': every tensor fp32 / bf16x3")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps also run the side measurements (call-by-call and other-dtype / other-launch-form legs, '
+                         'frames from host memory, the hipEvent roofline leg, the pipelined-vs-plain replay, CPU baselines, other '
+                         'workloads); without it the run stops after the timed steps and prints the headline line')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
     ap.add_argument('--single-block', action='store_true', help='time the --steps steps as ONE block instead of min(10, K) blocks')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps write what the last timed step returned to its caller as DIR/<name>.npy (float32, < 64 MB)')
-    ap.add_argument('--no-self-check', action='store_true', help='skip the pipelined-vs-plain bitwise replay on fresh handles')
-    ap.add_argument('--no-nlspn', action='store_true', help='skip the side measurements (2layers, NLSPN, CostDCNet)')
+    ap.add_argument('--no-self-check', action='store_true',
+                    help='with --full: skip the pipelined-vs-plain bitwise replay on fresh handles and the other-dtype / other-launch-form legs')
+    ap.add_argument('--no-nlspn', action='store_true', help='with --full: skip the other workloads (2layers, NLSPN, CostDCNet, ...)')
     ap.add_argument('--streams-per-gpu', type=int, default=1,
                     help='config 4 only (independent frame streams): this many streams -- own adapted parameters, Adam state and hipGraphs each -- '
                          'per GPU; the headline (and the default) is 1')
@@ -963,9 +973,12 @@ def main():
         t[rank] = per_rank_ms[0]
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         per_rank_ms = [float(x) for x in t.cpu()]
+    pipe_active = eng.get_option('pipelined_active')          # (read before the profiling leg switches the handle to one stream)
+    finite = bool(torch.isfinite(info).all().item())
+    # The side legs below run with --full only; a plain run goes straight to its JSON line.
     # the same K steps call by call with no next frame announced (plain ptta_step): reported beside the metric
     plain_ms = None
-    if pipe and world == 1:
+    if args.full and pipe and world == 1:
         for i in range(3):
             eng.step(*frames[i % nframes])
         pb = []
@@ -998,7 +1011,7 @@ def main():
             ob.append(1e3 * (time.perf_counter() - tp) / k_steps)
         e2.close()
         return float(np.median(ob)), len(ob)
-    if world == 1 and not args.no_self_check:
+    if args.full and world == 1 and not args.no_self_check:
         od = 'fp32' if args.dtype == 'mixed' else 'mixed'
         ms_, nb_ = side_run(od, options or None)
         other_dtype_ms = {'dtype': od, 'ms_per_step': ms_, 'blocks': nb_}
@@ -1009,7 +1022,7 @@ def main():
     # dataloader hands it over (src/tta_main.py:519-523): pinned triple buffer + copy stream, frame k+1 travels while frame k
     # is adapted.  Never `value` (that one is HBM-resident by contract).
     from_host = None
-    if world == 1:
+    if args.full and world == 1:
         from proxytta.staging import FrameStager
         host_frames = [synth.synthetic_frame(500 + i, H, W, 1) for i in range(nframes)]
         st = FrameStager(1, H, W)
@@ -1043,29 +1056,55 @@ def main():
     # Roofline leg: the timed region above replays a hipGraph, inside which kernels cannot be
     # bracketed by events, so the SAME K steps are re-run kernel by kernel right here with every
     # launch of the dominant kernel class bracketed by hipEvents on its launch stream.
-    pipe_active = eng.get_option('pipelined_active')          # (read before the profiling leg switches the handle to one stream)
-    eng.profile(True)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        eng.step(*frames[i % nframes])
-    torch.cuda.synchronize()
-    instrumented_ms = 1e3 * (time.perf_counter() - t1) / args.steps
-    prof = [eng.profile_read(k) for k in range(len(CLASSES))]
-    # dominant kernel = conv32_s1_x3_kernel<T, RELU, *> (+ its fused first-layer form): the stride-1 convolutions with ReLU on load on maps above
-    # 1/4 resolution -- the class with the largest share of the step (roofline_by_class).  Rounds 1-4 priced it TOGETHER with the small-map
-    # kernel (conv32_s1_small_kernel, a different kernel bound by launch latency, not by HBM): that figure stays beside it for continuity.
-    ms, abytes, macs, launches = prof[0]
-    ms_b, abytes_b, macs_b, launches_b = [sum(x) for x in zip(prof[0], prof[1])]
-    eng.profile(False)
-    finite = bool(torch.isfinite(info).all().item())
+    if args.full:
+        eng.profile(True)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            eng.step(*frames[i % nframes])
+        torch.cuda.synchronize()
+        instrumented_ms = 1e3 * (time.perf_counter() - t1) / args.steps
+        prof = [eng.profile_read(k) for k in range(len(CLASSES))]
+        # dominant kernel = conv32_s1_x3_kernel<T, RELU, *> (+ its fused first-layer form): the stride-1 convolutions with ReLU on load on maps
+        # above 1/4 resolution -- the class with the largest share of the step (roofline_by_class).  Rounds 1-4 priced it TOGETHER with the
+        # small-map kernel (conv32_s1_small_kernel, a different kernel bound by launch latency, not by HBM): that figure stays beside it.
+        ms, abytes, macs, launches = prof[0]
+        ms_b, abytes_b, macs_b, launches_b = [sum(x) for x in zip(prof[0], prof[1])]
+        eng.profile(False)
     eq_plain = None
-    if pipe and world == 1 and not args.no_self_check:
+    if args.full and pipe and world == 1 and not args.no_self_check:
         eq_plain = pipelined_self_check(args.dtype, min(args.steps, 12), rank, options or None, keep)
 
     if rank == 0:
-        mixed = args.dtype == 'mixed'
         steps_per_s = world * args.steps / elapsed
+        out = {
+            'metric': 'TTA frames/sec (fwd+loss+bwd+Adam) at 352x1216', 'value': steps_per_s, 'unit': 'frames/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / args.steps,
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': DTYPE_TEXT[args.dtype],
+            'data': 'synthetic',
+            'config': {'workload': 'MSG_CHN 1layer meta, 352x1216 KITTI-shaped synthetic, 1 TTA step/frame, batch 1 per GPU',
+                       'parallelism': 'independent frame streams, dp%d, no collectives' % world, 'finite': finite,
+                       'cpu_affinity': affinity, 'hip_force_dev_kernarg': kernarg, 'options': options or 'defaults',
+                       'launch': ('hipGraph replay (option graph = 1)' if options.get('graph') else
+                                  'direct launches on the caller\'s stream + the handle\'s second and prefix streams (option graph = 0, the default)'),
+                       'frame_pipelining': ('on: every call names the next frame of the stream; the part of its forward upstream of the adapted layer (frozen RGB '
+                                            'encoder, sparse-depth pooling, stage-1/4 cascade down to decoder 1\'s last transposed conv) runs on a second stream '
+                                            'beside the current step; K timed calls = K prefixes + K remainders; identical results' if pipe else 'off'),
+                       # 1: ptta_step_pipelined ran as itself on the timed handle; 0: it degraded to ptta_step call by call (include/ptta.h)
+                       'pipelined_active': pipe_active,
+                       'rccl_ranks': world if (dist is not None and dist.get_backend() == 'nccl') else (0 if dist is None else None),
+                       'collective_backend': None if dist is None else dist.get_backend(),
+                       # False: a plain run -- the headline steps only; the side measurements (and the keys they fill) come with --full
+                       'full': args.full},
+            'timing': {'protocol': '%d timed steps in %d blocks (%s), each block bracketed by barrier + synchronize, MAX over ranks; ms_per_step = median block'
+                                   % (args.steps, nblocks, '+'.join(map(str, blocks))),
+                       'blocks': nblocks, 'steps_timed': args.steps, 'ms_per_step_median': 1e3 * elapsed / args.steps,
+                       'ms_per_step_min': 1e3 * min(block_s) / args.steps, 'ms_per_step_max': 1e3 * max(block_s) / args.steps,
+                       'per_rank_ms_per_step': {'min': min(per_rank_ms), 'median': float(np.median(per_rank_ms)), 'max': max(per_rank_ms),
+                                                'ranks': per_rank_ms, 'note': "each rank's own median block, before the MAX over ranks"}},
+        }
+    if rank == 0 and args.full:
+        mixed = args.dtype == 'mixed'
         # fp32 storage, bf16x3 arithmetic: 3 x 2 x MACs bf16 FLOP against 256 B of fp32 I/O per pixel -> 216 FLOP/B < ridge 312: HBM is the roof
         # (narrow launches: 1 x 2 x MACs against 128 B -> 144 FLOP/B: HBM again)
         achieved = abytes / (ms * 1e-3) / 1e9
@@ -1106,27 +1145,11 @@ def main():
         else:
             step_bytes = (ALG_ELEMENTS_PER_STEP - ALG_ELEMENTS_HOISTED) * 4
             step_note = 'alg_bytes_per_step excludes the constant zero-image RGB-encoder pass, hoisted out of the step'
-        out = {
-            'metric': 'TTA frames/sec (fwd+loss+bwd+Adam) at 352x1216', 'value': steps_per_s, 'unit': 'frames/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / args.steps,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': DTYPE_TEXT[args.dtype],
-            'data': 'synthetic',
-            'config': {'workload': 'MSG_CHN 1layer meta, 352x1216 KITTI-shaped synthetic, 1 TTA step/frame, batch 1 per GPU',
-                       'parallelism': 'independent frame streams, dp%d, no collectives' % world, 'finite': finite,
-                       'cpu_affinity': affinity, 'hip_force_dev_kernarg': kernarg,
-                       'other_dtype_same_run': other_dtype_ms, 'other_launch_form_same_run': graph_ms, 'options': options or 'defaults',
-                       'launch': ('hipGraph replay (option graph = 1)' if options.get('graph') else
-                                  'direct launches on the caller\'s stream + the handle\'s second and prefix streams (option graph = 0, the default)'),
-                       'frame_pipelining': ('on: every call names the next frame of the stream; the part of its forward upstream of the adapted layer (frozen RGB '
-                                            'encoder, sparse-depth pooling, stage-1/4 cascade down to decoder 1\'s last transposed conv) runs on a second stream '
-                                            'beside the current step; K timed calls = K prefixes + K remainders; identical results' if pipe else 'off'),
-                       'ms_per_step_without_frame_pipelining': plain_ms,
-                       # the timed path against plain ptta_step on fresh handles, bit for bit (null: not run -- N > 1 or --no-self-check)
-                       'pipelined_equals_plain': eq_plain,
-                       # 1: ptta_step_pipelined ran as itself on the timed handle; 0: it degraded to ptta_step call by call (include/ptta.h)
-                       'pipelined_active': pipe_active,
-                       'rccl_ranks': world if (dist is not None and dist.get_backend() == 'nccl') else (0 if dist is None else None),
-                       'collective_backend': None if dist is None else dist.get_backend()},
+        out['config'].update({'other_dtype_same_run': other_dtype_ms, 'other_launch_form_same_run': graph_ms,
+                              'ms_per_step_without_frame_pipelining': plain_ms,
+                              # the timed path against plain ptta_step on fresh handles, bit for bit (null: not run -- N > 1 or --no-self-check)
+                              'pipelined_equals_plain': eq_plain})
+        out.update({
             'step_roofline': {'alg_bytes_per_step': step_bytes, 'alg_flop_per_step': ALG_FLOP_PER_STEP,
                               'alg_bytes_reference_executes': ALG_ELEMENTS_PER_STEP * 4,
                               'alg_bytes_fp32_storage': (ALG_ELEMENTS_PER_STEP - ALG_ELEMENTS_HOISTED) * 4,
@@ -1142,20 +1165,14 @@ def main():
                               'mfma_frac_note': 'issued bf16 MFMA FLOP (bf16x3 launches counted 3x, single-MFMA launches 1x) / 2.5 PFLOP/s dense'},
             'roofline': roof,
             'roofline_by_class': by_class,
-            'timing': {'protocol': '%d timed steps in %d blocks (%s), each block bracketed by barrier + synchronize, MAX over ranks; ms_per_step = median block'
-                                   % (args.steps, nblocks, '+'.join(map(str, blocks))),
-                       'blocks': nblocks, 'steps_timed': args.steps, 'ms_per_step_median': 1e3 * elapsed / args.steps,
-                       'ms_per_step_min': 1e3 * min(block_s) / args.steps, 'ms_per_step_max': 1e3 * max(block_s) / args.steps,
-                       'per_rank_ms_per_step': {'min': min(per_rank_ms), 'median': float(np.median(per_rank_ms)), 'max': max(per_rank_ms),
-                                                'ranks': per_rank_ms, 'note': "each rank's own median block, before the MAX over ranks"}},
-        }
+        })
         if from_host is not None:
             out['from_host_memory'] = from_host
         if world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline()
     eng.close()
     if rank == 0:
-        if world == 1 and not args.no_nlspn:
+        if args.full and world == 1 and not args.no_nlspn:
             out['other_workloads'] = {'msg_chn_2layers': msgchn_2layers_workload(), 'nlspn': nlspn_workload(), 'costdcnet': costdcnet_workload(),
                                       'head_stage2': head_stage2_workload(), 'msg_chn_two_streams_per_gpu': two_streams_workload(dtype=args.dtype),
                                       'msg_chn_batch': msgchn_batch_workload(dtype=args.dtype),

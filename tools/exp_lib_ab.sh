@@ -9,7 +9,7 @@ if [ -f $L/libptta_hip.alt2.so ]; then cp $L/libptta_hip.alt2.so /tmp/libC.so; V
 for rep in $(seq 1 ${REPS:-3}); do
   for V in $VS; do
     cp /tmp/lib$V.so $L/libptta_hip.so
-    python3 bench.py --steps 50 --warmup 10 --no-nlspn --no-cpu-baseline 2>/dev/null | python3 -c "
+    python3 bench.py --full --steps 50 --warmup 10 --no-nlspn --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('lib $V rep $rep ms_per_step', round(d['ms_per_step'],4), 'plain', round(d['config']['ms_per_step_without_frame_pipelining'] or 0,4))"
   done
 done

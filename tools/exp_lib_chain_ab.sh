@@ -9,7 +9,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for V in $VS; do
     cp /tmp/lib$V.so $L/libptta_hip.so
     python3 tools/bench_chain.py 2>/dev/null | grep "1/[12] x" | cut -c1-70 | sed "s/^/lib $V rep $rep  /"
-    [ -n "$NOBENCH" ] || python3 bench.py --steps 50 --warmup 10 --no-self-check --no-nlspn --no-cpu-baseline 2>/dev/null | python3 -c "
+    [ -n "$NOBENCH" ] || python3 bench.py --full --steps 50 --warmup 10 --no-self-check --no-nlspn --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('lib $V rep $rep ms_per_step', round(d['ms_per_step'],4), ' '.join('%s %.0f' % (k, v['us_per_step']) for k,v in d['roofline_by_class'].items() if isinstance(v,dict)))"
   done
 done

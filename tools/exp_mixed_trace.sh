@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/mx; rm -rf $O; mkdir -p $O
 for DT in ${DTYPES:-mixed}; do
-  python3 bench.py --dtype $DT --steps 30 --warmup 10 --single-block --no-nlspn --no-cpu-baseline --no-self-check > $O/bench_$DT.json 2> $O/bench_$DT.err
+  python3 bench.py --full --dtype $DT --steps 30 --warmup 10 --single-block --no-nlspn --no-cpu-baseline --no-self-check > $O/bench_$DT.json 2> $O/bench_$DT.err
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$DT -o x -- python3 bench.py --dtype $DT --steps 20 --warmup 10 --single-block --no-nlspn --no-cpu-baseline --no-self-check > /dev/null 2> $O/trace_$DT.log
   python3 tools/trace_sequence.py $O/trace_$DT/x_kernel_trace.csv 25 > $O/seq_$DT.txt
   python3 tools/prof_top.py $O/trace_$DT 40 > $O/top_$DT.txt

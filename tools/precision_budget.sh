@@ -29,7 +29,7 @@ for CFG in "fp32:fp32:" "heads-only:mixed:proxy,backward" "backward-only:mixed:p
   run "$L" $D "$K" 64x96 10 "--frame0 100"
   run "$L gate below (head_bias 5, w_cos 300)" $D "$K" 64x96 3 "--w-cos 300 --head-bias 5.0"
   run "$L gate above (head_bias 3.5, w_cos 300)" $D "$K" 64x96 3 "--w-cos 300 --head-bias 3.5"
-  T=$(PTTA_BENCH_KEEP="$K" python3 bench.py --dtype $D --steps 40 --warmup 10 --single-block --no-nlspn --no-cpu-baseline --no-self-check 2>/dev/null | python3 -c "
+  T=$(PTTA_BENCH_KEEP="$K" python3 bench.py --full --dtype $D --steps 40 --warmup 10 --single-block --no-nlspn --no-cpu-baseline --no-self-check 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.3f ms/step pipelined, %.3f call by call' % (d['ms_per_step'], d['config']['ms_per_step_without_frame_pipelining']))")
   echo "== $L | step time at 352x1216 (one block of 40 steps, this box): $T" >> $OUT
