@@ -267,8 +267,8 @@ int ptta_set_image_norm(ptta_handle h, float divisor, const float* mean, const f
  * swapped -- so proj AND pred train in both directions (ptta_head_get_grad: has_grad = 1 for all twelve), proj_t's BatchNorm1d runs in train mode
  * like the other two, and the backbone's BatchNorm2d layers normalise with their LOADED running statistics (`train(prepare=True)`,
  * src/nlspn_model_adapt.py:360-368, src/costdcnet_model_adapt.py:418-430) -- ptta_load_weights keeps them for this purpose; BatchNorm3d and the
- * sparse encoder's BatchNorm1d stay in train mode as in the reference.  Not offered (-38) with PTTA_SYNCBN_ADAPT, a statistics exchange bound,
- * or (CostDCNet) sizes that need the dual-corner padding.
+ * sparse encoder's BatchNorm1d stay in train mode as in the reference.  Not offered (-38) with PTTA_SYNCBN_ADAPT, a statistics exchange of
+ * more than one rank in the plain form (ptta_head_set_form), or (CostDCNet) sizes that need the dual-corner padding.
  * ptta_head_bind: name in {proj,pred}.{0,3}.{weight,bias}, {proj,pred}.1.{weight,bias} (param + both Adam moments, device fp32,
  * caller-owned, updated in place) or proj_t.* (param only; bind all six or none).  After ptta_head_adam_step the handle's
  * packed copies of the updated head weights are re-derived, so TTA calls on the same handle see them; after an EXTERNAL
@@ -285,6 +285,24 @@ int ptta_head_adam_step(ptta_handle h, ptta_stream s);
 int ptta_head_step(ptta_handle h, const float* image, const float* sparse_depth, int reverse, float* loss_out, ptta_stream s);
 /* gradient of the last ptta_head_backward; *has_grad_host = 0 (and dst untouched) for parameters outside the graph */
 int ptta_head_get_grad(ptta_handle h, const char* name, float* dst, int64_t capacity, int* has_grad_host, ptta_stream s);
+
+/* SyncBatchNorm form of the stage-2 head trainer: what the reference's stage 2 always runs.  src/head_main.py:278 convert_syncbn() and :279
+ * distributed_data_parallel(rank) run before train(prepare=True) (:407, :417), and src/train_head.py:178 spawns one rank per visible GPU.
+ * PTTA_HEAD_FORM_PLAIN (the default) stays the unconverted single-process form described above.  Under PTTA_HEAD_FORM_SYNCBN:
+ *   NLSPN      proj_t.1 (the EMA target's BatchNorm1d) is in eval mode: train_prepare's isinstance test (src/nlspn_model_adapt.py:360-368)
+ *              matches SyncBatchNorm, so it normalises with its loaded running statistics and leaves them untouched.
+ *   CostDCNet  proj_t.1, UNet3D's BatchNorm3d and the sparse encoder's BatchNorm1d are in eval mode with frozen affine
+ *              (src/costdcnet_model_adapt.py:418-430): running statistics bound by ptta_load_weights, untouched.
+ *   MSG_CHN    train_prepare is plain train() (src/msg_chn_model_adapt.py:435-440): one rank computes exactly the plain form.
+ *   every backbone, stat_sync world > 1 (ptta_set_stat_sync / ptta_set_stat_sync_rccl): proj.1 / pred.1 take the moments of the GLOBAL
+ *              batch in the forward and the backward; their running statistics use the global row count.  Before the head Adam the twelve
+ *              gradients, one arena, are averaged over the ranks as ONE message: ptta_set_grad_sync_rccl's communicator, or, without one,
+ *              the statistics exchange itself (its callback or its communicator) in chunks of its buffer (an fp64 sum, then / world:
+ *              bitwise the same on every rank; a buffer of at least the twelve tensors' numel makes it one message).
+ * Call before the first ptta_head_forward / ptta_head_step (-3 after it).  Refused (-38) on handles of PTTA_DTYPE_MIXED.  The form does
+ * not select the TTA adapted list (PTTA_SYNCBN_ADAPT): it applies to handles built without it.  The plain form returns -38 with world > 1. */
+enum { PTTA_HEAD_FORM_PLAIN = 0, PTTA_HEAD_FORM_SYNCBN = 1 };
+int ptta_head_set_form(ptta_handle h, int form);
 
 /* Geometric augmentation on device: Transforms.crop + horizontal_flip + vertical_flip
  * (src/transforms.py:337-407, 955-1034) in one pass over an N x C x H x W fp32 tensor:

@@ -297,6 +297,7 @@ struct costdc_engine : GNet {
         if (sync_adapt)      // no running statistics: batch statistics in train AND eval mode (synchronised over the ranks in train mode only)
             return cd_launch_sparse_bn(sp, f, res, level, b.C, adapted[b.ad_g].p, adapted[b.ad_b].p, nullptr, nullptr, nullptr, 1, 1, relu, out, s,
                                        train ? &stat_sync : nullptr, b.st) ? fail("sparse batch-norm " + n + " failed", -5) : 0;
+        if (bn_prepare == 2) train = false;      // the head trainer's SyncBatchNorm form: eval mode, from the loaded running statistics
         if (!train && (!b.rm || !b.rv)) return fail("running statistics of " + n + " not loaded", -3);
         // train: the reference evaluates the sparse encoder once per pass on the same input (CD:216, :237): two updates
         return cd_launch_sparse_bn(sp, f, res, level, b.C, b.g, b.b, b.rm, b.rv, b.nbt, train ? 1 : 0, 2, relu, out, s, &stat_sync) ? fail("sparse batch-norm " + n + " failed", -5) : 0;

@@ -177,6 +177,32 @@ int ptta_stat_sync(const PttaStatSync* sy, float* part, int nblocks, int C, int 
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
+// DistributedDataParallel's gradient mean over the exchange's hook (the stage-2 head trainer in the SyncBatchNorm form): fp32 gradients
+// widened into the fp64 exchange buffer, SUMMED over the ranks, divided by the world size and rounded back.  Every rank rounds the
+// same fp64 sum, so all ranks hold bitwise the same mean.  Chunks of the buffer's capacity (one message when the caller sized it).
+__global__ void grad_widen_kernel(const float* __restrict__ g, long n, double* __restrict__ out) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = (double)g[i];
+}
+__global__ void grad_mean_kernel(const double* __restrict__ in, long n, double inv_world, float* __restrict__ g) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) g[i] = (float)(in[i] * inv_world);
+}
+int ptta_grad_mean_sync(const PttaStatSync* sy, float* g, long n, hipStream_t s) {
+    if (!sy || !sy->on() || n < 1) return 0;
+    if (!sy->buf || sy->cap < 1) return -22;
+    const double inv_world = 1.0 / (double)sy->world;
+    for (long off = 0; off < n; off += sy->cap) {
+        const long m = n - off < sy->cap ? n - off : sy->cap;
+        long blocks = (m + 255) / 256; if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(grad_widen_kernel, dim3((int)blocks), dim3(256), 0, s, g + off, m, sy->buf);
+        if (hipGetLastError() != hipSuccess) return -5;
+        const int rc = sy->exchange((long long)m, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(grad_mean_kernel, dim3((int)blocks), dim3(256), 0, s, sy->buf, m, inv_world, g + off);
+        if (hipGetLastError() != hipSuccess) return -5;
+    }
+    return 0;
+}
+
 // forward finalize: per (pass, c): mean, inv, scale = gamma*inv, shift = beta - mean*scale   (st = [4][npass][C]).  One wave per channel,
 // the passes in order.  TRACKED BatchNorm (rm != null; CostDCNet's BatchNorm3d / BatchNorm1d): the momentum update of the running
 // statistics -- one per pass in order, `repeats` times each, exactly gbn_running_update_kernel's arithmetic -- and the eval-mode affine

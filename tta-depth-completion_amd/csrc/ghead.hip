@@ -11,6 +11,11 @@
 //                         (unlike MSG_CHN the reference branch is the EMA target, and proj trains in both directions)
 //     heads' BatchNorm1d  train mode (batch statistics, running statistics updated) -- proj_t's too on a single process (the isinstance test of
 //                         train_prepare names BatchNorm2d / SyncBatchNorm only)
+//   SyncBatchNorm form (ptta_head_set_form; src/head_main.py:278-279 convert_syncbn() + DDP, src/train_head.py:178 one rank per GPU):
+//     every BatchNorm is a SyncBatchNorm, so train_prepare's test matches them all: proj_t.1 and (CostDCNet) UNet3D's BatchNorm3d and the sparse
+//     encoder's BatchNorm1d evaluate from their loaded running statistics (bn_prepare = 2, Op::head_eval), buffers untouched;
+//     proj.1 / pred.1 stay in train mode and, with stat_sync.world > 1, exchange their forward moments and backward sums (gbn.hip);
+//     DDP's gradient mean over the twelve gradients' ONE arena before Adam: RCCL (grad_comm) or the exchange's hook
 //     prepare_loss        mean(2 - 2 <normalize(emb), normalize(ref)>)     src/external_model_adapt.py:524-541
 //     Adam                over prepare_parameters('head_selfsup_ema') = the twelve proj.* / pred.* tensors
 //
@@ -83,7 +88,7 @@ struct ProgSwap {
 int GNet::head_build(int reverse) {
     HeadTrain& h = head;
     if (!h.built) {
-        if (stat_sync.world > 1) return fail("the stage-2 head trainer has no SyncBatchNorm exchange", -38);
+        if (stat_sync.world > 1 && h.form != PTTA_HEAD_FORM_SYNCBN) return fail("the plain form of the stage-2 head trainer has no SyncBatchNorm exchange (ptta_head_set_form)", -38);
         NRUN(head_spec(&h.spec));
         const Tn xr = T[h.spec.x_real];
         const int per = xr.per, Hh = xr.H, Ww = xr.W;
@@ -130,6 +135,14 @@ int GNet::head_build(int reverse) {
         h.ops[0].x[0] = xa; h.ops[0].xw[0] = wa; h.ops[3].x[0] = xb; h.ops[3].xw[0] = wb;
         h.reverse = reverse;
     }
+    return 0;
+}
+
+int GNet::head_set_form(int form) {
+    if (form != PTTA_HEAD_FORM_PLAIN && form != PTTA_HEAD_FORM_SYNCBN) return fail("ptta_head_set_form: PTTA_HEAD_FORM_PLAIN or PTTA_HEAD_FORM_SYNCBN", -22);
+    if (head.stepped) return fail("ptta_head_set_form: the form is chosen before the first head step", -3);
+    if (form == PTTA_HEAD_FORM_SYNCBN && mixed) return fail("the SyncBatchNorm form of the stage-2 head trainer needs an fp32 handle", -38);
+    head.form = form;
     return 0;
 }
 
@@ -188,9 +201,12 @@ int GNet::head_reload(hipStream_t s) {
 }
 
 int GNet::head_forward(const float* image, const float* sparse, int reverse, float* emb_out, float* ref_out, hipStream_t s) {
+    if (stat_sync.world > 1 && head.form != PTTA_HEAD_FORM_SYNCBN) return fail("the plain form of the stage-2 head trainer has no SyncBatchNorm exchange (ptta_head_set_form)", -38);
     NRUN(head_build(reverse ? 1 : 0));
     HeadTrain& h = head;
     for (auto& a : h.adapted) if (!a.p || !a.m || !a.v) return fail("head parameter not bound: " + a.name, -3);
+    const bool sync_form = h.form == PTTA_HEAD_FORM_SYNCBN;
+    h.stepped = true;
     int nt = 0; for (auto& t : h.tgt) nt += t.p ? 1 : 0;
     if (nt != 0 && nt != 6) return fail("bind all six proj_t parameters or none", -3);
     h.bwd_ok = false;
@@ -220,9 +236,11 @@ int GNet::head_forward(const float* image, const float* sparse, int reverse, flo
     for (Op& ho : h.ops) {
         if (ho.kind != K_BN) continue;
         for (const Op& o : ops) if (o.kind == K_BN && o.bname == ho.bname) { ho.rm = o.rm; ho.rv = o.rv; ho.nbt = o.nbt; }
+        ho.head_eval = sync_form && ho.bname == "proj_t.1";        // train_prepare: '_t' in the name -> eval (SyncBatchNorm form)
+        if (ho.head_eval && (!ho.rm || !ho.rv)) return fail("running statistics of proj_t.1 not loaded (the SyncBatchNorm form evaluates it from them)", -3);
     }
     drop_graphs();
-    bn_prepare = 1;
+    bn_prepare = sync_form ? 2 : 1;
     const int rcf = head_features(image, sparse, s);
     bn_prepare = 0;
     fwd_valid = false;                   // not a forward ptta_backward may follow
@@ -262,6 +280,13 @@ int GNet::head_adam_step(hipStream_t s) {
         for (int k = 0; k < 12; ++k) { const Adapted& a = h.adapted[k]; h.adam_host[k] = PttaAdamEntry{a.p, a.m, a.v, h.gall + a.goff, a.n, off, 1}; off += a.n; }
         NCHK(hipMemcpyAsync(h.adam_tab, h.adam_host.data(), 12 * sizeof(PttaAdamEntry), hipMemcpyHostToDevice, s));
         h.adam_dirty = false;
+    }
+    if (h.form == PTTA_HEAD_FORM_SYNCBN) {            // DistributedDataParallel: the mean of the twelve gradients over the ranks, ONE message
+        if (grad_comm) { if (ptta_rccl_allreduce_mean_f32(grad_comm, h.gall, h.gall_n, (ptta_stream)s)) return fail(std::string("head gradient all-reduce: ") + ptta_rccl_last_error(), -5); }
+        else if (stat_sync.on() && stat_sync.world > 1) {       // the exchange's callback or communicator
+            const int rc = ptta_grad_mean_sync(&stat_sync, h.gall, h.gall_n, s);
+            if (rc) return fail("head gradient exchange failed", rc);
+        }
     }
     if (ptta_launch_adam_multi(h.adam_tab, 12, h.gall_n, h.hyper, h.step_dev, h.ticket, s)) return fail("adam failed", -5);
     drop_graphs();

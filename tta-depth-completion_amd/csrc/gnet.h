@@ -85,6 +85,7 @@ struct Op {
     int stat_to = -1;                 // (CONV) index of the BN op that consumes this conv's fused statistics
     bool first_raw = true, first_res = true;
     bool tracked = false;             // running statistics kept: updated in train mode (momentum 0.1), used in eval mode
+    bool head_eval = false;           // (tracked) eval mode inside a training forward: the stage-2 SyncBatchNorm form's proj_t.1
     bool act_first = false;           // with a residual: y = relu(act(bn(x)) + res) instead of relu(bn(x) + res)
     bool res_relu = true;             // with a residual: false = y = act(bn(x)) + res without the final ReLU (Res_Conv of the 2layers meta block)
     int stat_repeats = 1;             // the reference runs this layer `repeats` times per training forward on the same input
@@ -144,7 +145,8 @@ struct GNet {
     bool fwd_valid = false;
     int max_bn_C = 16;
     // stage-2 head trainer (ghead.hip): `train(prepare=True)` of the reference puts every BatchNorm2d of the backbone into eval mode -- while
-    // bn_prepare is set, BN ops that are not `tracked` (= the BatchNorm2d's) normalise every pass with their LOADED running statistics
+    // bn_prepare is set, BN ops that are not `tracked` (= the BatchNorm2d's) normalise every pass with their LOADED running statistics;
+    // 2 (the SyncBatchNorm form, ptta_head_set_form): the `tracked` ones too, from their bound running statistics, which stay untouched
     int bn_prepare = 0;
     PttaStatSync stat_sync;               // SyncBatchNorm exchange (ptta_set_stat_sync); world == 1: off
     void* grad_comm = nullptr;            // RCCL communicator of the gradient all-reduce inside step() (ptta_set_grad_sync_rccl)
@@ -204,7 +206,12 @@ struct GNet {
         int* step_dev = nullptr;
         int t_h[3][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};      // [proj, proj_t, pred][hidden, activation, out]
         int t_emb = -1, t_ref = -1;
+        int form = 0;                           // PTTA_HEAD_FORM_PLAIN / PTTA_HEAD_FORM_SYNCBN (ptta_head_set_form)
+        bool stepped = false;                   // a head forward ran: the form is fixed
     } head;
+    int head_set_form(int form);
+    // a tracked BatchNorm that a training forward evaluates from its running statistics (the SyncBatchNorm form of the head trainer)
+    bool bn_eval_in_train(const Op& o) const { return o.tracked && (o.head_eval || bn_prepare == 2); }
     int head_build(int reverse);
     int head_bind(const char* name, float* p, float* m, float* v);
     int head_set_hparams(float lr, float b1, float b2, float eps, float wd, float tau, int adam_step, hipStream_t s);

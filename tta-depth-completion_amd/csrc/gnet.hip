@@ -94,7 +94,7 @@ int GNet::run_conv_fwd(const Op& o, bool train, hipStream_t s) {
             a.wl2 = (const uint4*)cw.ff_l2; a.six_B = (o.yw == W_BOTH && train) ? y.B / 2 : y.B;
         }
         if ((mixed & 1) && train && o.yw != W_GRAD) a.x1_from_B = o.yw == W_BOTH ? y.B / 2 : 0;     // the proxy frames' products: one MFMA
-        if (o.stat_to >= 0 && (train || !ops[o.stat_to].tracked) && !(bn_prepare && !ops[o.stat_to].tracked)) {
+        if (o.stat_to >= 0 && (train || !ops[o.stat_to].tracked) && !(bn_prepare && !ops[o.stat_to].tracked) && !bn_eval_in_train(ops[o.stat_to])) {
             a.stat_part = ops[o.stat_to].part; a.stat_C = y.C; a.stat_npass = (o.yw == W_BOTH && train) ? 2 : 1;
         }
         int rc;
@@ -128,10 +128,12 @@ int GNet::run_bn_fwd(const Op& o, bool train, hipStream_t s) {
         if (ptta_launch_gbn_apply(x, res, y, 1, o.act, o.st_eval, o.res_relu ? 1 : 0, s, o.act_first ? 1 : 0)) return fail("batch-norm " + o.bname + " (prepare) launch failed", -5);
         return 0;
     }
-    if (o.tracked && !train) {                              // eval mode: running statistics
+    if (o.tracked && (!train || bn_eval_in_train(o))) {     // eval mode: running statistics
         if (!o.rm || !o.rv) return fail("running statistics of " + o.bname + " not loaded", -3);
-        // the affine of the running statistics is left behind by the training forward's finalize; computed here only after a load()
-        if (!o.st_eval_valid) {
+        // the affine of the running statistics is left behind by the training forward's finalize; computed here only after a load() --
+        // and on every pass of proj_t.1 in the head trainer's SyncBatchNorm form (its affine moves with the EMA; the running statistics of the
+        // modules bn_prepare == 2 evaluates do not move, so their cached affine holds)
+        if (!o.st_eval_valid || o.head_eval) {
             if (ptta_launch_gbn_eval_affine(bn_gamma(o), bn_beta(o), o.rm, o.rv, BN_EPS, x.C, o.st_eval, s)) return fail("batch-norm " + o.bname + " (eval) launch failed", -5);
             o.st_eval_valid = true;
         }

@@ -1117,7 +1117,8 @@ int ptta_launch_bn_finalize(const float* part, int row_blocks, int R, int N, con
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __restrict__ part, int row_blocks, int R, int N,
                                        const float* __restrict__ gamma, const float* __restrict__ invstd,
                                        float* gscale, float* c1, float* c2, float* dgamma, float* dbeta,
-                                       double* k12 = nullptr, const float* __restrict__ b0 = nullptr, const float* __restrict__ mean = nullptr) {
+                                       double* k12 = nullptr, const float* __restrict__ b0 = nullptr, const float* __restrict__ mean = nullptr,
+                                       float dscale = 1.f) {
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= N) return;
@@ -1130,7 +1131,7 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
     if (lane != 0) return;
     c1[c] = (float)(s1 / R); c2[c] = (float)(s2 / R);
     gscale[c] = gamma[c] * invstd[c];
-    if (dgamma) { dgamma[c] = (float)s2; dbeta[c] = (float)s1; }     // d gamma = sum g * xhat, d beta = sum g (stage-2 head trainer)
+    if (dgamma) { dgamma[c] = (float)(s2 * dscale); dbeta[c] = (float)(s1 * dscale); }     // d gamma = sum g * xhat, d beta = sum g (stage-2 head trainer)
     if (k12) {      // heads v2 (head_bwd_finish_kernel): k2 = gs c2 inv, k1 = gs c1 + k2 (b0 - mean), in double
         const double gs = (double)gamma[c] * (double)invstd[c];
         const double k2 = gs * (s2 / R) * (double)invstd[c];
@@ -1140,9 +1141,9 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
 
 int ptta_launch_bn_bwd_finalize(const float* part, int row_blocks, int R, int N, const float* gamma, const float* invstd,
                                 float* gscale, float* c1, float* c2, hipStream_t s, float* dgamma, float* dbeta,
-                                double* k12, const float* b0, const float* mean) {
+                                double* k12, const float* b0, const float* mean, float dscale) {
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((N + 3) / 4), dim3(256), 0, s, part, row_blocks, R, N, gamma,
-                       invstd, gscale, c1, c2, dgamma, dbeta, k12, b0, mean);
+                       invstd, gscale, c1, c2, dgamma, dbeta, k12, b0, mean, dscale);
     PTTA_CHECK_LAUNCH();
     return 0;
 }

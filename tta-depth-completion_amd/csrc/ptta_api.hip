@@ -102,7 +102,9 @@ struct ptta_ctx {
                    float *sv_mean = nullptr, *sv_inv = nullptr, *sv_scale = nullptr, *sv_shift = nullptr;     // proj BatchNorm state of its FIRST application
                    int* step = nullptr; unsigned* ticket = nullptr; PttaAdamEntry *tab = nullptr, *etab = nullptr;
                    std::vector<PttaAdamEntry> tab_host, etab_host; int tab_n = 0; long tab_total = 0, etab_total = 0; int tab_mode = -1; bool etab_dirty = true;
-                   int reverse = 1; bool fwd_ok = false, bwd_ok = false; } head;
+                   int reverse = 1; bool fwd_ok = false, bwd_ok = false;
+                   float* garena = nullptr; long garena_n = 0;      // the twelve gradients, one arena: the gradient mean is ONE message
+                   int form = 0; bool stepped = false; } head;    // PTTA_HEAD_FORM_* (ptta_head_set_form); a head forward ran: the form is fixed
     int skip_dec3 = 0;               // stage-2 head forward: no depth output
     int head_swap = 0;               // heads_forward order: 0 = emb from the proxy pass (TTA, stage-2 reverse), 1 = emb from the real pass
     float *meta_w = nullptr, *meta_b = nullptr;      // 1layer aliases of adapted[0].p / adapted[1].p
@@ -2343,10 +2345,13 @@ static int head_init(ptta_ctx* c) {
     if (c->nl) return c->fail("the stage-2 head trainer is built for MSG_CHN handles", -38);
     if (c->bf16) return c->fail("the stage-2 head trainer needs an fp32 handle", -38);
     if (c->dual) return c->fail("stage 2 runs on sizes divisible by 16 (the reference pads only in the 'adapt' forward, src/msg_chn_model_adapt.py:54-140)", -38);
-    if (c->stat_sync.world > 1) return c->fail("the stage-2 head trainer has no SyncBatchNorm exchange", -38);
+    if (c->stat_sync.world > 1 && c->head.form != PTTA_HEAD_FORM_SYNCBN) return c->fail("the plain form of the stage-2 head trainer has no SyncBatchNorm exchange (ptta_head_set_form)", -38);
     auto& h = c->head;
     h.prm.resize(12); h.tgt.resize(6);
-    for (int k = 0; k < 12; ++k) { h.prm[k].name = HEAD_NAMES[k]; h.prm[k].n = head_numel(k); h.prm[k].g = c->falloc((size_t)h.prm[k].n); }
+    h.garena_n = 0; for (int k = 0; k < 12; ++k) h.garena_n += head_numel(k);
+    h.garena = c->falloc((size_t)h.garena_n);
+    long goff = 0;
+    for (int k = 0; k < 12; ++k) { h.prm[k].name = HEAD_NAMES[k]; h.prm[k].n = head_numel(k); h.prm[k].g = h.garena + goff; goff += h.prm[k].n; }
     for (int k = 0; k < 6; ++k) { h.tgt[k].name = std::string("proj_t.") + (HEAD_NAMES[k] + 5); h.tgt[k].n = head_numel(k); }
     h.hyper = c->falloc(8); h.tau2 = c->falloc(2); h.loss = c->falloc(1); h.loss_part = c->falloc(1024);
     const int chunks = ptta_linear_wgrad_chunks(c->Rg, nullptr);
@@ -2386,6 +2391,16 @@ static int head_reload(ptta_ctx* c, int k, hipStream_t s) {
         BNorm& b = c->bn[base];
         HIPCHK(hipMemcpyAsync(is_w ? b.gamma : b.beta, e.p, 512 * 4, hipMemcpyDeviceToDevice, s));
     }
+    return 0;
+}
+
+int ptta_head_set_form(ptta_handle c, int form) {
+    if (!c) return -1;
+    NLFWD(c->nl->head_set_form(form));
+    if (form != PTTA_HEAD_FORM_PLAIN && form != PTTA_HEAD_FORM_SYNCBN) return c->fail("ptta_head_set_form: PTTA_HEAD_FORM_PLAIN or PTTA_HEAD_FORM_SYNCBN", -22);
+    if (c->head.stepped) return c->fail("ptta_head_set_form: the form is chosen before the first head step", -3);
+    if (form == PTTA_HEAD_FORM_SYNCBN && c->mixed) return c->fail("the SyncBatchNorm form of the stage-2 head trainer needs an fp32 handle", -38);
+    c->head.form = form;
     return 0;
 }
 
@@ -2433,7 +2448,9 @@ int ptta_head_forward(ptta_handle c, const float* image, const float* sparse, in
     RUN(head_init(c));
     auto& h = c->head;
     hipStream_t s = (hipStream_t)s_;
+    if (c->stat_sync.world > 1 && h.form != PTTA_HEAD_FORM_SYNCBN) return c->fail("the plain form of the stage-2 head trainer has no SyncBatchNorm exchange (ptta_head_set_form)", -38);
     for (int k = (reverse ? 6 : 0); k < 12; ++k) if (!h.prm[k].p) return c->fail(std::string("head parameter not bound: ") + HEAD_NAMES[k], -3);
+    h.stepped = true;
     // _update_head(): proj_t <- tau proj_t + (1 - tau) proj, BEFORE the heads run (network_exp_msg_chn_adapt.py:682,691)
     int nt = 0; for (auto& e : h.tgt) nt += e.p ? 1 : 0;
     if (nt != 0 && nt != 6) return c->fail("bind all six proj_t parameters or none", -3);
@@ -2472,6 +2489,9 @@ int ptta_head_backward(ptta_handle c, float* loss_out, ptta_stream s_) {
     if (loss_out) HIPCHK(hipMemcpyAsync(loss_out, h.loss, 4, hipMemcpyDeviceToDevice, s));
     for (int k = 0; k < 12; ++k) h.has_grad[k] = false;
     auto G = [&](int k) { h.has_grad[k] = true; return h.prm[k].g; };
+    // the SyncBatchNorm form with an exchange bound (the forward's mlp_forward exchanges the moments whenever one is)
+    const bool sync = h.form == PTTA_HEAD_FORM_SYNCBN && c->stat_sync.on();
+    const int world = c->stat_sync.world > 1 ? c->stat_sync.world : 1;
     // one MLP: out = Linear3(relu(BN(Linear0(x)))).  g: d out; hid: pre-BN hidden; x: MLP input (K wide); st_*: BN state of THIS application
     auto mlp_backward = [&](const char* name, int k0, const float* g, const float* hid, const void* x, int K,
                             const float* st_mean, const float* st_inv, const float* st_scale, const float* st_shift, float* dx) -> int {
@@ -2482,6 +2502,11 @@ int ptta_head_backward(ptta_handle c, float* loss_out, ptta_stream s_) {
         ga.eH = hid; ga.escale = st_scale; ga.eshift = st_shift; ga.emean = st_mean; ga.einv = st_inv; ga.part = c->bn_part;
         ga.x3 = c->x3; ga.Whi = l3.Wthi; ga.Wlo = l3.Wtlo; ga.Wil = l3.Wtil;
         RUN(ptta_launch_gemm(ga, s));
+        if (sync) {       // SyncBatchNorm backward: the two sums of the GLOBAL batch; d gamma / d beta keep the local share (DDP averages them)
+            RUN(ptta_stat_sync(&c->stat_sync, c->bn_part, ptta_gemm_part_blocks(ga), 512, 1, s));
+            RUN(ptta_launch_bn_bwd_finalize(c->bn_part, ptta_gemm_part_blocks(ga), (int)R * world, 512, bn.gamma, st_inv, c->bnb_gscale, c->bnb_c1, c->bnb_c2, s,
+                                            G(k0 + 2), G(k0 + 3), nullptr, nullptr, nullptr, 1.f / (float)world));
+        } else
         RUN(ptta_launch_bn_bwd_finalize(c->bn_part, ptta_gemm_part_blocks(ga), (int)R, 512, bn.gamma, st_inv, c->bnb_gscale, c->bnb_c1, c->bnb_c2, s,
                                         G(k0 + 2), G(k0 + 3)));
         LinWgradArgs w0; w0.G = c->gmask; w0.Gh = hid; w0.gscale = c->bnb_gscale; w0.gc1 = c->bnb_c1; w0.gc2 = c->bnb_c2; w0.gmean = st_mean; w0.ginv = st_inv;
@@ -2517,6 +2542,10 @@ int ptta_head_adam_step(ptta_handle c, ptta_stream s_) {
         h.tab_n = 12 - k0; h.tab_total = off;
         HIPCHK(hipMemcpyAsync(h.tab, h.tab_host.data(), h.tab_host.size() * sizeof(PttaAdamEntry), hipMemcpyHostToDevice, s));
         h.tab_mode = h.reverse;
+    }
+    if (h.form == PTTA_HEAD_FORM_SYNCBN) {                    // DistributedDataParallel: the mean of the head gradients over the ranks, ONE message
+        if (c->grad_comm) { if (ptta_rccl_allreduce_mean_f32(c->grad_comm, h.garena, h.garena_n, s_)) return c->fail(std::string("head gradient all-reduce: ") + ptta_rccl_last_error(), -5); }
+        else if (c->stat_sync.on() && c->stat_sync.world > 1) RUN(ptta_grad_mean_sync(&c->stat_sync, h.garena, h.garena_n, s));      // the exchange's callback or communicator
     }
     RUN(ptta_launch_adam_multi(h.tab, h.tab_n, h.tab_total, h.hyper, h.step, h.ticket, s));
     c->drop_graphs();                                         // the TTA graph holds no head weights by value, but stay conservative

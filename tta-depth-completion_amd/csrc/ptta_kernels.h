@@ -115,6 +115,7 @@ struct PttaStatSync {
     }
 };
 int ptta_stat_sync(const PttaStatSync* sy, float* part, int nblocks, int C, int npass, hipStream_t s);      // gbn.hip
+int ptta_grad_mean_sync(const PttaStatSync* sy, float* g, long n, hipStream_t s);                          // gbn.hip: mean over the ranks
 
 // ---- heads.hip --------------------------------------------------------------------------------
 struct GemmArgs {
@@ -168,7 +169,8 @@ int ptta_launch_bn_finalize(const float* part, int row_blocks, int R, int N, con
                             float* mean, float* invstd, float* scale, float* shift, hipStream_t s);
 int ptta_launch_bn_bwd_finalize(const float* part, int row_blocks, int R, int N, const float* gamma, const float* invstd,
                                 float* gscale, float* c1, float* c2, hipStream_t s, float* dgamma = nullptr, float* dbeta = nullptr,
-                                double* k12 = nullptr, const float* b0 = nullptr, const float* mean = nullptr);    // k12: [k1 512 | k2 512] for ptta_launch_head_bwd_finish
+                                double* k12 = nullptr, const float* b0 = nullptr, const float* mean = nullptr,     // k12: [k1 512 | k2 512] for ptta_launch_head_bwd_finish
+                                float dscale = 1.f);       // d gamma / d beta x dscale (1 / world: the local share of exchanged sums)
 
 // ---- heads_n.hip: the heads of the mixed mode (narrow storage, one bf16 MFMA per product) --------
 struct HnGemmArgs {

@@ -23,6 +23,8 @@ PTTA_META_1LAYER = 0
 PTTA_META_2LAYERS = 1
 PTTA_DTYPE_F32 = 0
 PTTA_DTYPE_MIXED = 1
+PTTA_HEAD_FORM_PLAIN = 0
+PTTA_HEAD_FORM_SYNCBN = 1
 PTTA_ABI_VERSION = 2           # include/ptta.h; checked against ptta_version() at load
 CONV_S1, CONV_S2, CONV_T2 = 0, 1, 2
 
@@ -73,6 +75,7 @@ SIGNATURES = [
     ('ptta_head_adam_step', c_int, [_P, _P]),
     ('ptta_head_step', c_int, [_P, _P, _P, c_int, _P, _P]),
     ('ptta_head_get_grad', c_int, [_P, c_char_p, _P, c_int64, POINTER(c_int), _P]),
+    ('ptta_head_set_form', c_int, [_P, c_int]),
     ('ptta_crop_flip', c_int, [_P, _P] + [c_int] * 6 + [_P] * 5),
     ('ptta_rotate', c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
     ('ptta_resize_crop', c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P]),

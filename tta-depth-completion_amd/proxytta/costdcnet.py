@@ -117,6 +117,8 @@ class CostDCNetModel_Adapt(MsgChnModel_Adapt):
         with batch statistics in train AND eval mode (its running statistics are dropped, :364-372) -- the library's
         PTTA_SYNCBN_ADAPT engine, whose sparse encoder has a backward for its BatchNorm gamma / beta."""
         super().convert_syncbn(apex)
+        if getattr(self, '_head_syncbn', False):    # stage 2: the head trainer's SyncBatchNorm form, the TTA list unchanged
+            return
         if self.prepare_mode is not None:
             self._set_adapted()
 

@@ -131,3 +131,20 @@ def shared_parameter_step(engine, image, sparse, validity=None, loss_image=None,
         engine.set_grad(k, g)
     engine.adam_step()
     return info, depth
+
+
+def shared_head_step(engine, image, sparse, reverse=True, group=None):
+    """Stage 2 across ranks (src/train_head.py:178 spawns one rank per GPU; src/head_main.py:278-279 convert_syncbn() + DDP): every
+    rank runs the fused head step on its slice of the batch in the SyncBatchNorm form (engine.set_head_form(1) before the first head
+    call).  proj.1 / pred.1 exchange their statistics over `group` and the twelve head gradients are averaged as ONE message before the
+    head Adam, both through the library's exchange hook (engine.enable_stat_sync: gloo or RCCL through torch.distributed), or on the
+    library's own communicator after engine.enable_rccl_sync().  Every rank then holds the same head parameters.  Returns the loss."""
+    from . import _lib
+    if getattr(engine, '_head_form', _lib.PTTA_HEAD_FORM_PLAIN) != _lib.PTTA_HEAD_FORM_SYNCBN:
+        raise RuntimeError('shared_head_step: engine.set_head_form(PTTA_HEAD_FORM_SYNCBN) before the first head call')
+    on = dist.is_available() and dist.is_initialized()
+    if (not getattr(engine, '_rccl_grads', False) and on and dist.get_world_size(group) > 1
+            and getattr(engine, '_head_sync_group', ()) is not group):
+        engine.enable_stat_sync(group)
+        engine._head_sync_group = group
+    return engine.head_step(image, sparse, reverse)

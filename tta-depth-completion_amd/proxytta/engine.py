@@ -319,7 +319,8 @@ class Engine:
         if world <= 1:
             self._chk(self.lib.ptta_set_stat_sync(self.handle, None, None, None, 0, 1), 'ptta_set_stat_sync')
             return
-        buf = torch.zeros(4 * 2 * 1024, device=self.device, dtype=torch.float64)
+        self._stat_sync_how = ('callback', group)
+        buf = torch.zeros(self._exchange_numel(), device=self.device, dtype=torch.float64)
 
         def _allreduce(user, ptr_, count, stream):
             try:
@@ -348,7 +349,8 @@ class Engine:
             comm, world = D.rccl_communicator()
         self._keep['rccl'] = comm
         if stats:
-            buf = torch.zeros(4 * 2 * 1024, device=self.device, dtype=torch.float64)
+            self._stat_sync_how = ('rccl', comm, world)
+            buf = torch.zeros(self._exchange_numel(), device=self.device, dtype=torch.float64)
             self._keep['stat_sync'] = (buf, None)
             self._chk(self.lib.ptta_set_stat_sync_rccl(self.handle, c_void_p(comm), c_void_p(buf.data_ptr()), buf.numel(), int(world)), 'ptta_set_stat_sync_rccl')
         if grads:
@@ -361,13 +363,43 @@ class Engine:
         self._rccl_grads = False
         self._keep.pop('stat_sync', None)
 
+    def _exchange_numel(self):
+        """Length of the statistics exchange buffer: the SyncBatchNorm form of the head trainer averages its twelve gradients through the
+        same exchange when no gradient communicator is set, so it gets room for them in ONE message."""
+        n = 4 * 2 * 1024
+        if getattr(self, '_head_form', 0) == _lib.PTTA_HEAD_FORM_SYNCBN:
+            n = max(n, sum(ts[0].numel() for k, ts in self._keep.items() if k.startswith('head/') and len(ts) == 3))
+        return n
+
+    def _fit_head_exchange(self):
+        """An exchange enabled before the heads were bound (or before the form was chosen) is grown to hold their gradients."""
+        kept = self._keep.get('stat_sync')
+        if kept is None or kept[0].numel() >= self._exchange_numel():
+            return
+        how = self._stat_sync_how
+        if how[0] == 'callback':
+            self.enable_stat_sync(how[1])
+        else:
+            buf = torch.zeros(self._exchange_numel(), device=self.device, dtype=torch.float64)
+            self._keep['stat_sync'] = (buf, None)
+            self._chk(self.lib.ptta_set_stat_sync_rccl(self.handle, c_void_p(how[1]), c_void_p(buf.data_ptr()), buf.numel(), int(how[2])),
+                      'ptta_set_stat_sync_rccl')
+
     # ---- stage-2 head trainer (include/ptta.h "Stage-2 head trainer"; src/head_main.py:464-480) ------------
+    def set_head_form(self, form):
+        """PTTA_HEAD_FORM_PLAIN (0) or PTTA_HEAD_FORM_SYNCBN (1, src/head_main.py:278-279 convert_syncbn() + DDP): before the first
+        head step.  An enabled statistics exchange grows to hold the head gradients in one message, whatever the order of the calls."""
+        self._chk(self.lib.ptta_head_set_form(self.handle, int(form)), 'ptta_head_set_form')
+        self._head_form = int(form)
+        self._fit_head_exchange()
+
     def bind_head(self, name, param, exp_avg=None, exp_avg_sq=None):
         ts = [t for t in (param, exp_avg, exp_avg_sq) if t is not None]
         for t in ts:
             assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
         self._keep['head/' + name] = ts
         self._chk(self.lib.ptta_head_bind(self.handle, name.encode(), ptr(param), ptr(exp_avg), ptr(exp_avg_sq)), 'ptta_head_bind')
+        self._fit_head_exchange()
 
     def set_head_hparams(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, tau=0.999, adam_step=-1):
         self._chk(self.lib.ptta_head_set_hparams(self.handle, lr, betas[0], betas[1], eps, weight_decay, tau, int(adam_step), _stream()),

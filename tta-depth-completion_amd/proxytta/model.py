@@ -13,7 +13,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import synth
+from . import _lib, synth
 from .engine import ADAPTED, HEAD_TARGETS, Engine, adapted_names
 
 CANONICAL_LOSS_TYPE = 'adapt_meta_selfsup_seq_ema_reverse'
@@ -251,6 +251,8 @@ class MsgChnModel_Adapt(object):
         if not getattr(eng, '_heads_bound', False):
             if getattr(self, '_head_names', None) is None:
                 raise RuntimeError('prepare_parameters(\'head_selfsup_ema\') must be called before a head forward (head_main.py:268)')
+            if getattr(self, '_head_syncbn', False):
+                eng.set_head_form(_lib.PTTA_HEAD_FORM_SYNCBN)
             params = dict(self.model.named_parameters())
             state = getattr(self, '_head_state', None) or {}
             for k in self._head_names:
@@ -263,6 +265,8 @@ class MsgChnModel_Adapt(object):
             hp = getattr(self, '_head_hp', None) or dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, tau=0.999)
             eng.set_head_hparams(adam_step=getattr(self, '_head_t', 0), **hp)
             eng._head_t = getattr(self, '_head_t', 0)
+            if getattr(self, '_head_syncbn', False):
+                eng.enable_stat_sync()          # after the binds: its buffer holds the head gradients too (no-op with one rank)
             eng._heads_bound = True
         return eng
 
@@ -345,7 +349,13 @@ class MsgChnModel_Adapt(object):
     def convert_syncbn(self, apex=False):
         """SyncBatchNorm.convert_sync_batchnorm (msg_chn_model_adapt.py:547-556): from now on train-mode BatchNorm
         statistics are those of the GLOBAL batch.  With one rank that is what the engine computes anyway; with
-        several ranks the statistics are exchanged inside proxytta.distributed.shared_parameter_step."""
+        several ranks the statistics are exchanged inside proxytta.distributed.shared_parameter_step.
+        After prepare_parameters('head_selfsup_ema') this is stage 2 (src/head_main.py:268, then :278): the head engines take the
+        SyncBatchNorm form (include/ptta.h ptta_head_set_form) and the TTA adapted list stays what it is."""
+        if getattr(self, '_head_names', None) is not None:
+            self._head_syncbn = True
+            self._clear_engines()
+            return
         self.sync_bn = True
         for eng in self._engines.values():
             eng.enable_stat_sync()

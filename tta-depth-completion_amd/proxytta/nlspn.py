@@ -99,6 +99,8 @@ class NlspnModel_Adapt(MsgChnModel_Adapt):
 
     def convert_syncbn(self, apex=False):
         super().convert_syncbn(apex)
+        if getattr(self, '_head_syncbn', False):    # stage 2: the head trainer's SyncBatchNorm form, the TTA list unchanged
+            return
         if self.prepare_mode is not None:           # heads exist: the adapted list grows to the 94 tensors of the DDP run
             self._set_adapted()
 
