@@ -1486,7 +1486,7 @@ int ptta_launch_conv32_first(const Conv32Args& a, const ConvInArgs& f, void* a_o
     const bool bwd_form = f.mask != nullptr;
     if (bwd_form && (!f.mask_bits || !a.mask_bits)) return 1;
     if (a.naive || (!a.bf16 && !a.x3) || a.mode != CONV_S1 || a.add2 || f.naive) return 1;
-    // (a second output = masked result + one addend: the backward form only -- d z4 = d s0_2 + up2^T(d e3_0), ptta_api.hip backbone_backward)
+    // (a second output = masked result + one addend: the backward form only -- d z4 = d s0_2 + up2^T(d e3_0), msgchn_backward.hip backbone_backward)
     if ((a.add1 != nullptr) != (a.out_sum != nullptr) || (a.out_sum && !bwd_form)) return 1;
     if (bwd_form ? (a.relu_in || !a.mask || a.up || f.cin != 1) : (!a.relu_in || a.mask != nullptr)) return 1;
     if (f.cin < 1 || f.cin > 3 || f.up || f.add1 || f.B != a.B || f.H != a.Hin || f.W != a.Win) return 1;

@@ -453,7 +453,7 @@ struct GNet {
         return 0;
     }
 
-    // ---- the C-ABI entry points (ptta_api.hip forwards to these) ---------------------------------------------------------
+    // ---- the C-ABI entry points (ptta_api.hip, msgchn_step.hip and msgchn_head.hip forward to these) ---------------------------------------------------------
     int set_hparams(const ptta_hparams* h, hipStream_t s) { if (h->max_input_depth != hp.max_input_depth) drop_graphs(); hp = *h; return upload_hparams(s); }
     int set_image_norm(float div, const float* mean, const float* stdv);
     int bind_adapted(const char* name, float* p, float* m, float* v);

@@ -302,7 +302,7 @@ int ptta_launch_loss_forward(const float* depth, const float* image, const float
     return 0;
 }
 
-// The two halves of ptta_launch_loss_forward as separate launches and the finalisation as its own (the fused step's two branches, ptta_api.hip
+// The two halves of ptta_launch_loss_forward as separate launches and the finalisation as its own (the fused step's two branches, msgchn_step.hip
 // step_tail: the depth terms behind decoder 3 on one stream, the cosine rows behind the heads on the other -- neither waits for the other's
 // forward): same kernels, same partials, same finalisation.
 int ptta_launch_loss_depth_part(const float* depth, const float* image, const float* sparse, const float* validity, float max_input_depth,
@@ -331,7 +331,7 @@ __device__ __forceinline__ void depth_grad_body(int bx, int nbx, const float* __
     __shared__ float fin[3 + LOSS_FIN_MAXN];
     const size_t plane = (size_t)H * W;
     const size_t total = (size_t)N * plane;
-    if (w3 && cnt) loss_coef_block(cnt, N, H, W, w3, fin);           // fused step, the loss values reduced elsewhere (step_tail, ptta_api.hip)
+    if (w3 && cnt) loss_coef_block(cnt, N, H, W, w3, fin);           // fused step, the loss values reduced elsewhere (step_tail, msgchn_step.hip)
     else if (w3) loss_finalize_block(ws, N, H, W, R, has_cos, w3, fin, bx == 0 ? loss_info : nullptr, ws);       // fused step
     const float cx = w3 ? fin[1] : ws[WS_SCAL + 1], cy = w3 ? fin[2] : ws[WS_SCAL + 2];
     for (size_t gi = (size_t)bx * blockDim.x + threadIdx.x; gi < total; gi += (size_t)nbx * blockDim.x) {

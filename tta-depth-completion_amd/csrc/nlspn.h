@@ -1,5 +1,5 @@
-// Backbones built on the generic layer-graph engine (gnet.h): constructors only; every C-ABI entry point of ptta_api.hip
-// forwards to the GNet methods.
+// Backbones built on the generic layer-graph engine (gnet.h): constructors only; every C-ABI entry point that takes a handle
+// (ptta_api.hip, msgchn_step.hip, msgchn_head.hip) forwards to the GNet methods.
 #pragma once
 #include "gnet.h"
 

@@ -224,7 +224,7 @@ int ptta_launch_loss_backward(const float* depth, const float* image, const floa
                               int N, int H, int W, float* ws, float* gdepth, float* gref, hipStream_t s, const float* w3_fused = nullptr,
                               float* loss_info_fused = nullptr, int cos_partials_ready = 0, int valid_count_ready = 0);
 // the valid-weight partials of the sparse-depth term: all the depth gradient's coefficients depend on (a function of the step's inputs alone);
-// with valid_count_ready the depth gradient reads them instead of the loss partials and reports nothing (fused step: ptta_api.hip step_tail)
+// with valid_count_ready the depth gradient reads them instead of the loss partials and reports nothing (fused step: msgchn_step.hip step_tail)
 int ptta_launch_loss_valid_count(const float* sparse, const float* validity, int N, int H, int W, float* ws, hipStream_t s);
 // (cos_partials_ready with emb == NULL: the depth gradient alone, its in-kernel finalisation includes the cosine term and the gate)
 // validity may be NULL in both calls: where(sparse > 0, 1, sparse) is then computed on the fly (src/tta_main.py:583-586)
