@@ -463,6 +463,32 @@ int ptta_op_conv32(const float* in_nhwc, const float* weight, const float* bias,
  * kernel + its reduction) to *us_per_call_host; reps = 0 and us_per_call_host = NULL compute once.  Synchronises. */
 int ptta_op_gwgrad(const float* x_nhwc, const float* gy_nhwc, float* gw, float* gb, int b, int h, int w, int ci, int co, int impl,
                    int reps, float* us_per_call_host, ptta_stream s);
+/* Test hook: ONE convolution of the generic op-list engine (NLSPN, CostDCNet, the 2layers block) on fp32 NHWC device views, packed and
+ * launched the way the engine does it.  Sources x0 [b][hin][win] (c0 channels, pixel stride ld0 >= c0) and, channel-concatenated behind
+ * it, optional x1 (c1, ld1; NULL and 0 without); output view y [b][hout][wout] (co channels, pixel stride ldy; channels outside the view
+ * are not touched).  weight as the state dict holds it: [co][c0 + c1][k][k], [c0 + c1][co][k][k] for PTTA_GCONV_T2, [co][ci][3][1][1]
+ * with PTTA_GCONV_VERT (a 3x1x1 Conv3d run as a vertical 3-tap convolution: k = 3, stride 1); bias [co] or NULL; k 1 or 3.
+ * geom: PTTA_GCONV_S1 (hout = hin), _S2 (stride 2, hout = ceil(hin / 2)), _T2 (transposed, stride 2, output_padding 1: hout = 2 hin).
+ * act: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 sigmoid, applied to (accumulate ? y : 0) + bias + convolution.
+ * impl 0: the matrix-core kernels (channel counts multiples of 8, of 16 for the strided geometries; 16-byte aligned sources); impl 1: the
+ * direct fp32 kernels, one launch per source.  Arithmetic of impl 0, per image of the batch: images below six_b bf16x6, the others
+ * bf16x3; images from x1_from_b on (pass b or more for none) one bf16 product (x_hi w_hi), with PTTA_GCONV_X1_W2 two (x_hi (w_hi + w_lo)).
+ * PTTA_GCONV_DGRAD: the data gradient instead, as the engine's backward sweep runs it: x0 = the gradient of the forward OUTPUT
+ * ([b][hin][win][c0], c0 = the forward convolution's output channels, no x1), weight = the FORWARD weight of a co -> c0 convolution of
+ * geometry geom, y = the gradient of its input (S2: hout = 2 hin or 2 hin - 1; T2: hout = hin / 2).
+ * stat_npass 1 or 2 (S1, impl 0): the fused BatchNorm partial sums of the epilogue, summed over the tiles, to stat_host [npass][2][co] =
+ * {sum y, sum y^2} per equal slice of the batch; 0 and NULL without.  form_host (may be NULL): for the strided geometries of impl 0 the
+ * kernel form the launcher took -- 0: one channel tile per wave, 1: two, 2: K split over the block's waves -- else -1.
+ * -22 for arguments outside this, -12 out of memory.  Synchronises. */
+#define PTTA_GCONV_S1 0
+#define PTTA_GCONV_S2 1
+#define PTTA_GCONV_T2 2
+#define PTTA_GCONV_VERT 1
+#define PTTA_GCONV_X1_W2 2
+#define PTTA_GCONV_DGRAD 4
+int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y,
+                  int co, int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl,
+                  int flags, int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, ptta_stream s);
 /* Diagnostic (tools/bench_chain.py): `reps` dependent launches of one stride-1 32->32 convolution (fp32 NHWC, default arithmetic) captured
  * into one hipGraph and replayed `replays` times: microseconds per launch INSIDE a replayed graph.  epi_flags: 2 = ReLU mask from `aux`,
  * 4 = skip addition of `aux`, 8 = the same chain launched directly (no graph), 16 = the layer loop (ONE launch per `reps` layers with a

@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from proxytta import synth
-from tests.util import ONE, TWO, golden_hp, make_engine, rel_mae
+from tests.gconv_cases import TOL
+from tests.util import ONE, TWO, assert_elementwise, golden_hp, make_engine, rel_mae
 
 pytestmark = pytest.mark.gpu
 
@@ -31,6 +32,17 @@ def _torch_conv(x_nhwc, w, b, mode, relu):
     return y.permute(0, 2, 3, 1).contiguous()
 
 
+def _conv_bound(x_nhwc, w, b, mode, relu, tol):
+    """(float64 reference, componentwise bound tol * (|x| (*) |w| + |bias|)) of _torch_conv; tol from the CPU emulations of
+    oracle/gconv_arith.py (tests/gconv_cases.py TOL)."""
+    xd = x_nhwc.double()
+    if relu:
+        xd = xd.clamp(min=0)
+    ref = _torch_conv(xd, w.double(), None if b is None else b.double(), mode, False)
+    mag = _torch_conv(xd.abs(), w.double().abs(), None if b is None else b.double().abs(), mode, False)
+    return ref, tol * mag
+
+
 @pytest.mark.parametrize('naive', [True, False])
 @pytest.mark.parametrize('mode', [0, 1, 2])
 @pytest.mark.parametrize('relu', [False, True])
@@ -44,6 +56,7 @@ def test_op_conv32_forward(mode, relu, naive):
     got = op_conv32(x.cuda(), w.cuda(), b.cuda(), mode, relu_in=relu, in_major=(mode == 2), naive=naive).cpu()
     assert got.shape == ref.shape
     assert rel_mae(got, ref) < 2e-6
+    assert_elementwise(got, *_conv_bound(x, w, b, mode, relu, TOL['fp32']), 'conv32 forward mode %d' % mode)
 
 
 @pytest.mark.parametrize('naive', [True, False])
@@ -61,6 +74,8 @@ def test_op_conv32_input_gradient(mode, naive):
     bmode, in_major, flip = {0: (0, True, True), 1: (2, True, False), 2: (1, False, False)}[mode]
     got = op_conv32(gy.cuda(), w.cuda(), None, bmode, in_major=in_major, flip=flip, naive=naive).cpu()
     assert rel_mae(got, gx) < 2e-6
+    wg = w.transpose(0, 1).flip(2, 3) if mode == 0 else w      # the gradient as a convolution of gy: S1 flipped, S2 -> T2 and T2 -> S2 as stored
+    assert_elementwise(got, *_conv_bound(gy, wg, None, bmode, False, TOL['fp32']), 'conv32 input gradient mode %d' % mode)
 
 
 @pytest.mark.parametrize('relu', [False, True])
@@ -76,6 +91,7 @@ def test_op_conv32_bf16x3(shape, relu):
     ref = _torch_conv(x, wt, bias, 0, relu)
     got = op_conv32(x.cuda(), wt.cuda(), bias.cuda(), 0, relu_in=relu, x3=True).cpu()
     assert rel_mae(got, ref) < 2e-5
+    assert_elementwise(got, *_conv_bound(x, wt, bias, 0, relu, TOL['x3']), 'conv32 bf16x3')
     # and the backward re-packing through the same kernel
     xr = x.clone().requires_grad_(True)
     y = _torch_conv(xr, wt, None, 0, False)
@@ -139,6 +155,9 @@ def test_op_conv32_narrow(shape):
             got = op_conv32(x.cuda(), w.cuda(), b.cuda(), mode, relu_in=relu, in_major=(mode == 2), dtype='narrow').cpu()
             assert rel_mae(got, ref) < 4e-3, (mode, relu)        # output rounded to bf16 (2^-9 per element)
             assert rel_mae(got, ref.bfloat16().float()) < 4e-4, (mode, relu)     # ... and beyond that rounding only fp32 summation order
+            # per element: one MFMA on the rounded operands (TOL['x1r']) plus half an ulp of bf16 (at most 2^-8 of the value) on the stored output
+            r64, bnd = _conv_bound(xr, wr, b, mode, relu, TOL['x1r'])
+            assert_elementwise(got, r64, bnd + 2.0 ** -8 * (r64.abs() + bnd), 'conv32 narrow mode %d' % mode)
 
 
 def _run_golden(name, impl, golden_dir):

@@ -938,18 +938,26 @@ int ptta_launch_gconv_x3(const GX3Args& a, int ks, hipStream_t s) {
     return 0;
 }
 
+// The launch form of the strided / transposed kernel, from the sizes alone (the launcher below and ptta_op_gconv's form_host both call
+// this).  GX3_FORM_KSPLIT: few pixels and a long K loop (the 1/8 and 1/16-resolution layers): one item per block, K split over its
+// waves, one channel tile per wave; otherwise GX3_FORM_NCO2, two channel tiles per wave, where the tile count and the kernel allow it,
+// or GX3_FORM_PLAIN, one.  (measured on the NLSPN step, same box: one tile 24.83 ms, two 24.36, four 24.47)
+int ptta_gconv_x3_strided_form(const GX3Args& a, int ks, int mode, int win, long* nitems_out) {
+    const int Wt = mode == 2 ? win : a.W;
+    const long nitems = (long)a.B * ((Wt + 31) / 32) * (mode == 2 ? 2 : 1) * (mode == 1 ? (a.H + 1) / 2 : a.H);   // stride 2: two rows per wave
+    if (nitems_out) *nitems_out = nitems;
+    if (a.nchunks >= 4 && ((nitems + 3) / 4) * a.nnf < 1536) return GX3_FORM_KSPLIT;
+    return (ks != 3 || (a.nnf & 1)) ? GX3_FORM_PLAIN : GX3_FORM_NCO2;
+}
+
 // mode 1: stride-2 convolution (a.H/a.W = output size, input = hin x win); mode 2: stride-2 transposed convolution
 int ptta_launch_gconv_x3_strided(const GX3Args& a, int ks, int mode, int hin, int win, hipStream_t s) {
     if ((a.C0 & 15) || (a.C1 & 15) || (a.ld0 & 3) || (a.ld1 & 3) || (ks != 1 && ks != 3) || (mode != 1 && mode != 2)) return -22;
     if (a.nchunks != (a.C0 + 31) / 32 + (a.C1 + 31) / 32) return -22;
-    const int Wt = mode == 2 ? win : a.W;
-    const long nitems = (long)a.B * ((Wt + 31) / 32) * (mode == 2 ? 2 : 1) * (mode == 1 ? (a.H + 1) / 2 : a.H);   // stride 2: two rows per wave
-    // few pixels and a long K loop: split K over the block's waves
-    // few pixels and a long K loop (the 1/8 and 1/16-resolution layers): one item per block, K split over its waves, one channel
-    // tile per wave; otherwise two channel tiles per wave
-    const bool split = a.nchunks >= 4 && ((nitems + 3) / 4) * a.nnf < 1536;
-    // (measured on the NLSPN step, same box: one tile 24.83 ms, two 24.36, four 24.47)
-    const int nco = (split || ks != 3 || (a.nnf & 1)) ? 1 : 2;
+    long nitems = 0;
+    const int form = ptta_gconv_x3_strided_form(a, ks, mode, win, &nitems);
+    const bool split = form == GX3_FORM_KSPLIT;
+    const int nco = form == GX3_FORM_NCO2 ? 2 : 1;
     const int ngrp = a.nnf / nco;
     const long blocks = (split ? nitems : (nitems + 3) / 4) * ngrp;
     if (blocks < 1 || blocks > 0x7fffffffL) return -22;

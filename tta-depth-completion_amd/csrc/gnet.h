@@ -106,6 +106,51 @@ struct Adapted { std::string name; long n = 0, goff = 0; float *p = nullptr, *m 
 __global__ void gnet_pad_channels_kernel(const float* __restrict__ src, int lds_, int C, float* __restrict__ dst, int Cp, long npix);
 inline int nb(long total) { long b = (total + 255) / 256; if (b > 16384) b = 16384; if (b < 1) b = 1; return (int)b; }
 
+// ---- weight packing: the engine's (GNet::load, GNet::repack_adapted) and the stand-alone hook's (ptta_op_gconv) ----------------------
+// matrix-core fragments from the packed matrices cw.wf / cw.wb, for whichever of the forward (cw.mf) and the data gradient (cw.mb) use them
+inline void pack_frags(GConvW& cw, hipStream_t s) {
+    if (cw.vcol) {
+        // 3x1x1 Conv3d: the matrix-core kernel's VERT form takes the three vertical taps only (canonical taps 1, 4, 7)
+        const long ts = (long)cw.Ci * cw.Co;
+        if (cw.mf) ptta_gfrag_pack(cw.wf + ts, cw.Co, 3 * ts, 3, cw.C0, cw.C1, 0, cw.C0, cw.Co, cw.ff_hi, cw.ff_lo, s, cw.ff_l2);
+        if (cw.mb) ptta_gfrag_pack(cw.wb + ts, cw.Ci, 3 * ts, 3, cw.Co, 0, 0, 0, cw.Ci, cw.fb_hi, cw.fb_lo, s);
+        return;
+    }
+    const int KK = cw.k * cw.k;
+    if (cw.mf && cw.Ci_real) ptta_gfrag_pack(cw.wf, cw.Co, (long)cw.Ci_real * cw.Co, KK, cw.Ci_real, 0, 0, 0, cw.Co, cw.ff_hi, cw.ff_lo, s, cw.ff_l2);
+    else if (cw.mf) ptta_gfrag_pack(cw.wf, cw.Co, (long)cw.Ci * cw.Co, KK, cw.C0, cw.C1, 0, cw.C0, cw.Co, cw.ff_hi, cw.ff_lo, s, cw.ff_l2);
+    if (cw.mb && !cw.Ci_real) ptta_gfrag_pack(cw.wb, cw.Ci, (long)cw.Co * cw.Ci, KK, cw.Co, 0, 0, 0, cw.Ci, cw.fb_hi, cw.fb_lo, s);
+    // second source at a channel offset that is not a tile boundary: its own fragment set (columns C0.. of the packed matrix)
+    if (cw.fb1_hi) ptta_gfrag_pack(cw.wb + cw.C0, cw.Ci, (long)cw.Co * cw.Ci, KK, cw.Co, 0, 0, 0, cw.C1, cw.fb1_hi, cw.fb1_lo, s);
+}
+// src: Conv2d (Co,Ci,k,k) / ConvTranspose2d (Ci,Co,k,k) / Linear (Co,Ci) weight
+inline void pack_conv_weight(GConvW& cw, const float* src, hipStream_t s) {
+    const int KK = cw.k * cw.k;
+    const int Ci = cw.Ci_real ? cw.Ci_real : cw.Ci;
+    if (!cw.transposed) {
+        // forward P[t][ci][co] = W[co][ci][t]; data gradient P[t][co][ci] = W[co][ci][flip t] (stride 1: a conv with
+        // flipped taps; stride 2: consumed by the transposed kernel, which wants the taps unflipped)
+        ptta_gpack(src, cw.wf, KK, Ci, cw.Co, KK, (long)Ci * KK, 0, s);
+        ptta_gpack(src, cw.wb, KK, cw.Co, Ci, (long)Ci * KK, KK, cw.stride == 1 ? 1 : 0, s);
+    } else {
+        // ConvTranspose2d weight (Ci, Co, k, k): forward P[t][ci][co] = W[ci][co][t]; gradient = stride-2 conv with
+        // P[t][co][ci] = W[ci][co][t]
+        ptta_gpack(src, cw.wf, KK, Ci, cw.Co, (long)cw.Co * KK, KK, 0, s);
+        ptta_gpack(src, cw.wb, KK, cw.Co, Ci, KK, (long)cw.Co * KK, 0, s);
+    }
+    pack_frags(cw, s);
+}
+// src: Conv3d (Co, Ci, 3, 1, 1) weight of a cw.vcol layer: the vertical taps of a 3x3 filter over [D][H*W] (the other six taps of
+// cw.wf / cw.wb stay as allocated: zero)
+inline void pack_vcol_weight(GConvW& cw, const float* src, hipStream_t s) {
+    const int Ci = cw.Ci_real ? cw.Ci_real : cw.Ci;
+    for (int ky = 0; ky < 3; ++ky) {
+        ptta_gpack(src + ky, cw.wf + (size_t)(ky * 3 + 1) * Ci * cw.Co, 1, Ci, cw.Co, 3, (long)Ci * 3, 0, s);
+        ptta_gpack(src + (2 - ky), cw.wb + (size_t)(ky * 3 + 1) * cw.Co * Ci, 1, cw.Co, Ci, (long)Ci * 3, 3, 0, s);
+    }
+    pack_frags(cw, s);
+}
+
 }  // namespace gnet
 
 struct GNet {
@@ -382,38 +427,9 @@ struct GNet {
     }
 
     // ---- weights ---------------------------------------------------------------------------------------------------
-    void pack_frags(GConvW& cw, hipStream_t s) {
-        if (cw.vcol) {
-            // 3x1x1 Conv3d: the matrix-core kernel's VERT form takes the three vertical taps only (canonical taps 1, 4, 7)
-            const long ts = (long)cw.Ci * cw.Co;
-            if (cw.mf) ptta_gfrag_pack(cw.wf + ts, cw.Co, 3 * ts, 3, cw.C0, cw.C1, 0, cw.C0, cw.Co, cw.ff_hi, cw.ff_lo, s, cw.ff_l2);
-            if (cw.mb) ptta_gfrag_pack(cw.wb + ts, cw.Ci, 3 * ts, 3, cw.Co, 0, 0, 0, cw.Ci, cw.fb_hi, cw.fb_lo, s);
-            return;
-        }
-        const int KK = cw.k * cw.k;
-        if (cw.mf && cw.Ci_real) ptta_gfrag_pack(cw.wf, cw.Co, (long)cw.Ci_real * cw.Co, KK, cw.Ci_real, 0, 0, 0, cw.Co, cw.ff_hi, cw.ff_lo, s, cw.ff_l2);
-        else if (cw.mf) ptta_gfrag_pack(cw.wf, cw.Co, (long)cw.Ci * cw.Co, KK, cw.C0, cw.C1, 0, cw.C0, cw.Co, cw.ff_hi, cw.ff_lo, s, cw.ff_l2);
-        if (cw.mb && !cw.Ci_real) ptta_gfrag_pack(cw.wb, cw.Ci, (long)cw.Co * cw.Ci, KK, cw.Co, 0, 0, 0, cw.Ci, cw.fb_hi, cw.fb_lo, s);
-        // second source at a channel offset that is not a tile boundary: its own fragment set (columns C0.. of the packed matrix)
-        if (cw.fb1_hi) ptta_gfrag_pack(cw.wb + cw.C0, cw.Ci, (long)cw.Co * cw.Ci, KK, cw.Co, 0, 0, 0, cw.C1, cw.fb1_hi, cw.fb1_lo, s);
-    }
-    // src: Conv2d (Co,Ci,k,k) / ConvTranspose2d (Ci,Co,k,k) / Linear (Co,Ci) weight
-    void pack_conv_weight(GConvW& cw, const float* src, hipStream_t s) {
-        const int KK = cw.k * cw.k;
-        const int Ci = cw.Ci_real ? cw.Ci_real : cw.Ci;
-        if (!cw.transposed) {
-            // forward P[t][ci][co] = W[co][ci][t]; data gradient P[t][co][ci] = W[co][ci][flip t] (stride 1: a conv with
-            // flipped taps; stride 2: consumed by the transposed kernel, which wants the taps unflipped)
-            ptta_gpack(src, cw.wf, KK, Ci, cw.Co, KK, (long)Ci * KK, 0, s);
-            ptta_gpack(src, cw.wb, KK, cw.Co, Ci, (long)Ci * KK, KK, cw.stride == 1 ? 1 : 0, s);
-        } else {
-            // ConvTranspose2d weight (Ci, Co, k, k): forward P[t][ci][co] = W[ci][co][t]; gradient = stride-2 conv with
-            // P[t][co][ci] = W[ci][co][t]
-            ptta_gpack(src, cw.wf, KK, Ci, cw.Co, (long)cw.Co * KK, KK, 0, s);
-            ptta_gpack(src, cw.wb, KK, cw.Co, Ci, KK, (long)cw.Co * KK, 0, s);
-        }
-        pack_frags(cw, s);
-    }
+    // (the packing itself: gnet::pack_frags / pack_conv_weight / pack_vcol_weight above, shared with ptta_op_gconv)
+    void pack_frags(GConvW& cw, hipStream_t s) { gnet::pack_frags(cw, s); }
+    void pack_conv_weight(GConvW& cw, const float* src, hipStream_t s) { gnet::pack_conv_weight(cw, src, s); }
     int load(const char* name_c, const void* tensor_, const int64_t* shape, int ndim, hipStream_t s);
     // adapted convolutions are re-packed from the bound tensors on every forward
     void repack_adapted(hipStream_t s) {

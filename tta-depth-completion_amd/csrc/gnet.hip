@@ -54,11 +54,7 @@ int GNet::load(const char* name_c, const void* tensor_, const int64_t* shape, in
     const int Ci = cw.Ci_real ? cw.Ci_real : cw.Ci;
     if (cw.vcol) {                                 // Conv3d (Co, Ci, 3, 1, 1): vertical taps of a 3x3 filter over [D][H*W]
         if (ndim != 5 || shape[0] != cw.Co || shape[1] != Ci || shape[2] != 3 || shape[3] != 1 || shape[4] != 1) return fail("shape mismatch for " + name, -22);
-        for (int ky = 0; ky < 3; ++ky) {
-            ptta_gpack(src + ky, cw.wf + (size_t)(ky * 3 + 1) * Ci * cw.Co, 1, Ci, cw.Co, 3, (long)Ci * 3, 0, s);
-            ptta_gpack(src + (2 - ky), cw.wb + (size_t)(ky * 3 + 1) * cw.Co * Ci, 1, cw.Co, Ci, (long)Ci * 3, 3, 0, s);
-        }
-        pack_frags(cw, s);
+        gnet::pack_vcol_weight(cw, src, s);
         cw.loaded = true;
         return 0;
     }

@@ -374,6 +374,9 @@ void ptta_gfrag_pack(const float* canon, long wld, long wts, int KK, int C0, int
 long ptta_gfrag_elems(int KK, int C0, int C1, int Co);
 int ptta_launch_gconv_x3(const GX3Args& a, int ks, hipStream_t s);
 int ptta_launch_gconv_x3_strided(const GX3Args& a, int ks, int mode, int hin, int win, hipStream_t s);
+// the kernel ptta_launch_gconv_x3_strided takes for these sizes (instantiation <.., KSPLIT, NCO>): <1, 1>, <1, 2> or <4, 1>
+enum { GX3_FORM_PLAIN = 0, GX3_FORM_NCO2 = 1, GX3_FORM_KSPLIT = 2 };
+int ptta_gconv_x3_strided_form(const GX3Args& a, int ks, int mode, int win, long* nitems_out = nullptr);
 long ptta_gwgrad_mfma_part_floats(long pixels, int Ci, int Co);
 // Adam applied by the weight gradient's reduction itself (gconv_mfma.hip gwgrad_mfma_reduce_kernel; <= 32 x 32 channels, the single-pair bf16x3 form only;
 // ptta_launch_gwgrad_mfma returns -22 for any other shape with ad.pw set): parameter + both

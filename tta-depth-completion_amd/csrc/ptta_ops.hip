@@ -1,6 +1,7 @@
 // Entry points that take no handle: outlier removal, evaluation metrics, the modulated deformable convolution, and the
-// stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_conv32_chain).
+// stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_gconv, ptta_op_conv32_chain).
 #include "msgchn_ctx.h"
+#include "gnet.h"
 
 using namespace msgchn;
 
@@ -127,6 +128,108 @@ int ptta_op_gwgrad(const float* x, const float* gy, float* gw, float* gb, int b,
     }
     if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
     (void)hipFree(part);
+    return rc;
+}
+
+// Stand-alone convolution of the generic engine on fp32 NHWC device views (tests): the weight is packed by the engine's own code
+// (gnet::pack_conv_weight / pack_vcol_weight) and launched ONCE the way GNet::run_conv_fwd / run_conv_bwd launch it -- the matrix-core
+// form (impl 0) or the direct fp32 form (impl 1, one launch per source).  include/ptta.h states the arguments.
+int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y, int co,
+                  int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl, int flags,
+                  int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    const bool vert = flags & PTTA_GCONV_VERT, dgrad = flags & PTTA_GCONV_DGRAD;
+    if (!x0 || !weight || !y || b < 1 || hin < 1 || win < 1 || hout < 1 || wout < 1 || c0 < 1 || c1 < 0 || co < 1 || ld0 < c0 || ldy < co ||
+        (c1 > 0) != (x1 != nullptr) || (c1 > 0 && ld1 < c1) || (k != 1 && k != 3) || geom < PTTA_GCONV_S1 || geom > PTTA_GCONV_T2 ||
+        act < GACT_NONE || act > GACT_SIGMOID || impl < 0 || impl > 1 || (flags & ~7) || six_b < 0 || six_b > b || x1_from_b < 0 ||
+        stat_npass < 0 || stat_npass > 2 || (accumulate & ~1)) return -22;
+    if (vert && (k != 3 || geom != PTTA_GCONV_S1)) return -22;
+    if (dgrad && (c1 > 0 || six_b > 0)) return -22;
+    if (stat_npass > 0 && (!stat_host || geom != PTTA_GCONV_S1 || impl != 0 || dgrad || (b % stat_npass))) return -22;
+    // the geometry that runs: a data gradient is the other strided geometry with the same weight tensor (gconv.hip)
+    const int run = !dgrad ? geom : (geom == PTTA_GCONV_S2 ? PTTA_GCONV_T2 : (geom == PTTA_GCONV_T2 ? PTTA_GCONV_S2 : PTTA_GCONV_S1));
+    const bool size_ok = run == PTTA_GCONV_S1 ? (hout == hin && wout == win)
+                       : run == PTTA_GCONV_S2 ? (hout == (hin + 1) / 2 && wout == (win + 1) / 2)
+                       // (the gradient of a stride-2 convolution over an odd-sized map: 2 hin - 1)
+                       : ((hout == 2 * hin || (dgrad && hout == 2 * hin - 1)) && (wout == 2 * win || (dgrad && wout == 2 * win - 1)));
+    if (!size_ok) return -22;
+    if (impl == 0 && ((((size_t)x0 | (size_t)x1) & 15) || (ld0 & 3) || (ld1 & 3))) return -22;   // the matrix-core kernels load 16 B
+    if (form_host) *form_host = -1;
+
+    gnet::GConvW cw;                                   // of the FORWARD convolution `weight` belongs to
+    cw.k = k; cw.stride = geom == PTTA_GCONV_S1 ? 1 : 2; cw.transposed = geom == PTTA_GCONV_T2 ? 1 : 0; cw.vcol = vert ? 1 : 0;
+    if (!dgrad) { cw.Ci = c0 + c1; cw.Co = co; cw.C0 = c0; cw.C1 = c1; }
+    else { cw.Ci = co; cw.Co = c0; cw.C0 = co; cw.C1 = 0; }
+    cw.mf = impl == 0 && !dgrad; cw.mb = impl == 0 && dgrad;
+    const int KK = k * k;
+    const size_t nw = (size_t)KK * cw.Ci * cw.Co;
+    const size_t nfrag = cw.mf ? (size_t)ptta_gfrag_elems(KK, cw.C0, cw.C1, cw.Co) : (cw.mb ? (size_t)ptta_gfrag_elems(KK, cw.Co, 0, cw.Ci) : 0);
+    const int tiles_pp = stat_npass ? ptta_gconv_x3_tiles(b / stat_npass, hout, wout) : 0;
+    const size_t nstat = (size_t)stat_npass * tiles_pp * 2 * co;
+    float* wbuf = nullptr; bf16_t* fbuf = nullptr; float* stat = nullptr;
+    int rc = 0;
+    if (hipMalloc((void**)&wbuf, 2 * nw * sizeof(float)) != hipSuccess || (nfrag && hipMalloc((void**)&fbuf, 3 * nfrag * sizeof(bf16_t)) != hipSuccess) ||
+        (nstat && hipMalloc((void**)&stat, nstat * sizeof(float)) != hipSuccess)) rc = -12;
+    if (!rc && (hipMemsetAsync(wbuf, 0, 2 * nw * sizeof(float), s) != hipSuccess || (nstat && hipMemsetAsync(stat, 0, nstat * sizeof(float), s) != hipSuccess))) rc = -5;
+    if (!rc) {
+        cw.wf = wbuf; cw.wb = wbuf + nw;
+        if (cw.mf) { cw.ff_hi = fbuf; cw.ff_lo = fbuf + nfrag; if (six_b > 0) cw.ff_l2 = fbuf + 2 * nfrag; }
+        if (cw.mb) { cw.fb_hi = fbuf; cw.fb_lo = fbuf + nfrag; }
+        if (vert) gnet::pack_vcol_weight(cw, weight, s); else gnet::pack_conv_weight(cw, weight, s);
+        GView xv[2], yv;
+        xv[0].p = (float*)x0; xv[0].C = c0; xv[0].ld = ld0; xv[1].p = (float*)x1; xv[1].C = c1; xv[1].ld = ld1;
+        for (GView& v : xv) { v.B = b; v.H = hin; v.W = win; }
+        yv.p = y; yv.B = b; yv.H = hout; yv.W = wout; yv.C = co; yv.ld = ldy;
+        if (impl == 0) {
+            GX3Args a;
+            a.x0 = x0; a.C0 = c0; a.ld0 = ld0;
+            if (c1 > 0) { a.x1 = x1; a.C1 = c1; a.ld1 = ld1; }
+            a.B = b; a.H = hout; a.W = wout;
+            a.whi = (const uint4*)(dgrad ? cw.fb_hi : cw.ff_hi); a.wlo = (const uint4*)(dgrad ? cw.fb_lo : cw.ff_lo);
+            a.nchunks = (a.C0 + 31) / 32 + (a.C1 + 31) / 32; a.nf0 = 0; a.nnf = (co + 31) / 32;
+            a.y = y; a.ldy = ldy; a.Cy = co; a.bias = bias; a.act = act; a.accumulate = accumulate; a.vert = vert ? 1 : 0;
+            if (six_b > 0) { a.wl2 = (const uint4*)cw.ff_l2; a.six_B = six_b; }
+            a.x1_from_B = x1_from_b; a.x1_w2 = (flags & PTTA_GCONV_X1_W2) ? 1 : 0;
+            if (stat) { a.stat_part = stat; a.stat_C = co; a.stat_npass = stat_npass; }
+            if (run == PTTA_GCONV_S1) rc = ptta_launch_gconv_x3(a, k, s);
+            else {
+                const int mode = run == PTTA_GCONV_T2 ? 2 : 1;
+                if (form_host) *form_host = ptta_gconv_x3_strided_form(a, k, mode, win);
+                rc = ptta_launch_gconv_x3_strided(a, k, mode, hin, win, s);
+            }
+        } else {
+            for (int sidx = 0; sidx < (c1 > 0 ? 2 : 1) && !rc; ++sidx) {
+                GConvArgs a;
+                a.x = xv[sidx]; a.y = yv; a.k = k;
+                if (!dgrad) {                          // GNet::run_conv_fwd: bias with the first source, the activation after the last
+                    a.w = cw.wf + (size_t)(sidx ? c0 : 0) * cw.Co; a.wld = cw.Co; a.wts = (long)cw.Ci * cw.Co;
+                    a.bias = sidx == 0 ? bias : nullptr;
+                    a.stride = cw.stride; a.transposed = cw.transposed;
+                    a.accumulate = (sidx > 0 || accumulate) ? 1 : 0; a.act = sidx == (c1 > 0 ? 1 : 0) ? act : GACT_NONE;
+                } else {                               // GNet::run_conv_bwd
+                    a.w = cw.wb; a.wld = cw.Ci; a.wts = (long)cw.Co * cw.Ci;
+                    a.bias = bias; a.act = act; a.accumulate = accumulate;
+                    a.stride = run == PTTA_GCONV_S1 ? 1 : 2; a.transposed = run == PTTA_GCONV_T2 ? 1 : 0;
+                }
+                rc = ptta_launch_gconv_direct(a, s);
+            }
+        }
+    }
+    std::vector<float> hstat;
+    if (!rc && nstat) {
+        hstat.resize(nstat);
+        if (hipMemcpyAsync(hstat.data(), stat, nstat * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) rc = -5;
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    if (!rc && nstat) {                                // [pass][tile][2][co] -> [pass][2][co], tiles summed in fp64
+        for (int pass = 0; pass < stat_npass; ++pass)
+            for (int j = 0; j < 2 * co; ++j) {
+                double v = 0.0;
+                for (int t = 0; t < tiles_pp; ++t) v += (double)hstat[((size_t)pass * tiles_pp + t) * 2 * co + j];
+                stat_host[(size_t)pass * 2 * co + j] = v;
+            }
+    }
+    (void)hipFree(wbuf); (void)hipFree(fbuf); (void)hipFree(stat);
     return rc;
 }
 

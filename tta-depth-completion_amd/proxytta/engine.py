@@ -506,3 +506,40 @@ def op_gwgrad(x_nhwc, gy_nhwc, impl='default', with_bias=True, reps=0):
     if rc != 0:
         raise RuntimeError('ptta_op_gwgrad failed (%d)' % rc)
     return gw, gb, (us.value if reps > 0 else None)
+
+
+GCONV_GEOMS = {'s1': 0, 's2': 1, 't2': 2}
+GCONV_ACTS = {'none': 0, 'relu': 1, 'lrelu': 2, 'sigmoid': 3}
+GCONV_IMPLS = {'mfma': 0, 'direct': 1}
+GCONV_FORMS = {-1: None, 0: 'plain', 1: 'nco2', 2: 'ksplit'}
+
+
+def op_gconv(x0, weight, y, x1=None, bias=None, k=3, geom='s1', act='none', accumulate=False, impl='mfma', vert=False, six_b=0,
+             x1_from_b=None, x1_w2=False, dgrad=False, stat_npass=0):
+    """Test hook: one convolution of the generic engine (include/ptta.h ptta_op_gconv) on fp32 NHWC device tensors.  x0 [b, hin, win, c0],
+    x1 [b, hin, win, c1] or None and y [b, hout, wout, co] may be channel slices of wider tensors (stride(-1) == 1, dense over pixels):
+    y is written in place.  weight / bias as the state dict holds them.  Returns (form, stats): the strided launch form ('plain', 'nco2',
+    'ksplit'; None for stride 1 and the direct form) and the fused statistics [stat_npass, 2, co] as float64, or None."""
+    lib = _lib.load()
+
+    def view(t):
+        b, h, w, c = t.shape
+        ld = t.stride(2)
+        assert t.dtype == torch.float32 and t.stride(3) == 1 and t.stride(1) == w * ld and t.stride(0) == h * w * ld and ld >= c
+        return c_void_p(t.data_ptr()), c, ld
+    b, hin, win, _ = x0.shape
+    hout, wout = y.shape[1], y.shape[2]
+    assert y.shape[0] == b and (x1 is None or tuple(x1.shape[:3]) == (b, hin, win))
+    p0, c0, ld0 = view(x0)
+    p1, c1, ld1 = view(x1) if x1 is not None else (None, 0, 0)
+    py, co, ldy = view(y)
+    stats = (ctypes.c_double * (stat_npass * 2 * co))() if stat_npass else None
+    form = c_int(-1)
+    flags = (1 if vert else 0) | (2 if x1_w2 else 0) | (4 if dgrad else 0)
+    rc = lib.ptta_op_gconv(p0, c0, ld0, p1, c1, ld1, ptr(weight.contiguous()), ptr(bias), py, co, ldy, b, hin, win, hout, wout, k,
+                           GCONV_GEOMS[geom], GCONV_ACTS[act], int(bool(accumulate)), GCONV_IMPLS[impl], flags, int(six_b),
+                           (1 << 30) if x1_from_b is None else int(x1_from_b), int(stat_npass), stats, byref(form), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_gconv failed (%d)' % rc)
+    st = torch.tensor(list(stats), dtype=torch.float64).view(stat_npass, 2, co) if stat_npass else None
+    return GCONV_FORMS[form.value], st
