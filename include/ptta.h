@@ -489,6 +489,36 @@ int ptta_op_gwgrad(const float* x_nhwc, const float* gy_nhwc, float* gw, float* 
 int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y,
                   int co, int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl,
                   int flags, int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, ptta_stream s);
+/* Test hook: ONE BatchNorm of the generic op-list engine (csrc/gbn.hip: every BatchNorm of NLSPN, CostDCNet and the heads, and the apply /
+ * backward launchers of the MSG_CHN 2layers block) on caller-supplied fp32 NHWC device views, launched the way the engine's forward and
+ * backward sweeps launch it, with the engine's scratch sizes.  A view is a pointer, its channel count and its pixel stride ld >= c;
+ * channels outside a view are not touched.  b images of h x w pixels hold npass (1 or 2) equal slices with their own statistics.
+ *   PTTA_GBN_TRAIN     x, optional res -> y and st [4][npass][c] = {mean, inv, scale, shift}.  part_in != NULL: caller-made partial sums
+ *                      [npass][nblocks_in][2][c] = {sum x, sum x^2} stand in for a convolution epilogue's and the statistics pass is
+ *                      skipped.  rm != NULL (with rv; nbt, st_eval optional): a tracked BatchNorm, running statistics updated npass *
+ *                      repeats times with `momentum`, st_eval [4][c] = the eval affine of the updated buffers.
+ *   PTTA_GBN_EVAL      st [4][c] from rm / rv, then y = the apply with npass = 1.
+ *   PTTA_GBN_BACKWARD  x and y over all passes; g, gx and optional gres (its presence says that the forward had a residual) over the
+ *                      b / npass images of pass 0; st from the forward.  dgamma / dbeta [c] may be NULL (frozen parameters).
+ * act: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 4 ELU.  world > 1: a SyncBatchNorm exchange whose collective multiplies the buffer by `world`
+ * (every rank holds the same data) -- the collapse / expand kernels, the R * world row count and the 1 / world gradient scale without a
+ * communicator.
+ * -22 BEFORE any launch for: c not a multiple of 4, ld < c or not a multiple of 4, a view, st or an [n][c] table not 16-byte aligned,
+ * views whose channel counts disagree, b not a multiple of npass, and the switch combinations no kernel computes in both directions
+ * (residual with res_relu = 0 and act != 0; residual with res_relu = 1, act_first = 1 and act != ReLU).  -12 out of memory.
+ * Synchronises. */
+#define PTTA_GBN_TRAIN 0
+#define PTTA_GBN_EVAL 1
+#define PTTA_GBN_BACKWARD 2
+typedef struct ptta_gbn_view { float* p; int c; int ld; } ptta_gbn_view;
+typedef struct ptta_gbn_args {
+    int mode, b, h, w, npass, act, act_first, res_relu, acc_gx, acc_gres, world, nblocks_in, repeats;
+    float eps, momentum;
+    ptta_gbn_view x, res, y, g, gx, gres;
+    const float* gamma; const float* beta; const float* part_in;
+    float* st; float* rm; float* rv; long long* nbt; float* st_eval; float* dgamma; float* dbeta;
+} ptta_gbn_args;
+int ptta_op_gbn(const ptta_gbn_args* a, ptta_stream s);
 /* Diagnostic (tools/bench_chain.py): `reps` dependent launches of one stride-1 32->32 convolution (fp32 NHWC, default arithmetic) captured
  * into one hipGraph and replayed `replays` times: microseconds per launch INSIDE a replayed graph.  epi_flags: 2 = ReLU mask from `aux`,
  * 4 = skip addition of `aux`, 8 = the same chain launched directly (no graph), 16 = the layer loop (ONE launch per `reps` layers with a

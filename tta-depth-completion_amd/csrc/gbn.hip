@@ -280,12 +280,26 @@ __global__ void gbn_apply_kernel(GView x, GView res, GView y, int npass, int act
     }
 }
 
+// Switch combinations no kernel here computes in both directions; every launcher refuses them (-22) so that an engine cannot grow into them:
+//   residual, res_relu = 0, act != none: with act_first = 0 the forward never applies act while the backward differentiates it; with
+//     act_first = 1 the backward takes the activation's mask from the saved act(v) + res instead of act(v)
+//   residual, res_relu = 1, act_first = 1, act != ReLU: the backward's inner mask is a ReLU's
+bool ptta_gbn_switches_ok(bool has_res, int act, int res_relu, int act_first) {
+    if (has_res && !res_relu && act != GACT_NONE) return false;
+    if (has_res && res_relu && act_first && act != GACT_RELU) return false;
+    return true;
+}
+static bool gbn_apply_views_ok(const GView& x, const GView& res, const GView& y) {
+    return !((x.C & 3) || (x.ld & 3) || (y.ld & 3) || (res.p && (res.ld & 3)));
+}
+
 // fused_blocks > 0: `part` was already filled by the producing convolution's epilogue ([pass][fused_blocks][2][C]), skip the
 // statistics pass
 int ptta_launch_gbn_forward(const GView& x, const GView& res, const GView& y, int npass, int act, float eps, const float* gamma,
                             const float* beta, float* part, float* st, hipStream_t s, int fused_blocks, int act_first, const PttaStatSync* sync,
                             float* rm, float* rv, long long* nbt, float momentum, int repeats, float* st_eval, int res_relu) {
     const int C = x.C, CT = C < 256 ? C : 256, nsub = 256 / CT;
+    if (!gbn_apply_views_ok(x, res, y) || !ptta_gbn_switches_ok(res.p != nullptr, act, res_relu, act_first)) return -22;     // before the first launch
     const size_t lds = (size_t)nsub * 2 * CT * sizeof(float);
     const long R = (long)(x.B / npass) * x.H * x.W;
     int blocks = (int)((R + nsub - 1) / nsub); if (blocks > GBN_BLOCKS) blocks = GBN_BLOCKS; if (blocks < 1) blocks = 1;
@@ -295,7 +309,6 @@ int ptta_launch_gbn_forward(const GView& x, const GView& res, const GView& y, in
     if (sync && sync->on()) { const int rc = ptta_stat_sync(sync, part, blocks, C, npass, s); if (rc) return rc; Rg = R * sync->world; }
     const GbnTrack tr{rm, rv, nbt, momentum, repeats, st_eval};
     hipLaunchKernelGGL(gbn_finalize_kernel, dim3(rm ? C : npass * C), dim3(256), 0, s, part, blocks, npass, C, Rg, eps, gamma, beta, st, tr);
-    if ((C & 3) || (x.ld & 3) || (y.ld & 3) || (res.p && (res.ld & 3))) return -22;
     const long total = (long)x.B * x.H * x.W * (C >> 2);
     long ab = (total + 255) / 256; if (ab > 16384) ab = 16384; if (ab < 1) ab = 1;
     hipLaunchKernelGGL(gbn_apply_kernel, dim3((int)ab), dim3(256), 0, s, x, res, y, npass, act, st, res_relu, act_first);
@@ -308,7 +321,7 @@ int ptta_gbn_part_floats(int C, int npass) { return npass * GBN_BLOCKS * 2 * C; 
 int ptta_launch_gbn_apply(const GView& x, const GView& res, const GView& y, int npass, int act, const float* st, int res_relu, hipStream_t s,
                           int act_first) {
     const int C = x.C;
-    if ((C & 3) || (x.ld & 3) || (y.ld & 3) || (res.p && (res.ld & 3))) return -22;
+    if (!gbn_apply_views_ok(x, res, y) || !ptta_gbn_switches_ok(res.p != nullptr, act, res_relu, act_first)) return -22;
     const long total = (long)x.B * x.H * x.W * (C >> 2);
     long ab = (total + 255) / 256; if (ab > 16384) ab = 16384; if (ab < 1) ab = 1;
     hipLaunchKernelGGL(gbn_apply_kernel, dim3((int)ab), dim3(256), 0, s, x, res, y, npass, act, st, res_relu, act_first);
@@ -380,6 +393,9 @@ int ptta_launch_gbn_backward(const GView& x, const GView& g, const GView& y, con
                              int res_relu, int acc_gx, int acc_gres, const float* gamma, const float* st, float* part, float* bw, float* dgamma,
                              float* dbeta, hipStream_t s, int act_first, const PttaStatSync* sync) {
     const int C = x.C, CT = C < 256 ? C : 256, nsub = 256 / CT;
+    // (the caller passes res_relu = 0 without a residual; gres stands for the residual of a block without the final ReLU)
+    if ((C & 3) || (x.ld & 3) || (g.ld & 3) || (y.ld & 3) || (gx.ld & 3) || (gres.p && (gres.ld & 3))) return -22;
+    if (!ptta_gbn_switches_ok(gres.p != nullptr || res_relu, act, res_relu, act_first)) return -22;
     const size_t lds = (size_t)nsub * 2 * CT * sizeof(float);
     GView x0 = x; x0.B = g.B;
     GView y0 = y; y0.B = g.B;
@@ -401,7 +417,6 @@ int ptta_launch_gbn_backward(const GView& x, const GView& g, const GView& y, con
     long Rg = R; float gsc = 1.f;
     if (sync && sync->on()) { const int rc = ptta_stat_sync(sync, part, blocks, C, 1, s); if (rc) return rc; Rg = R * sync->world; gsc = 1.f / (float)sync->world; }
     hipLaunchKernelGGL(gbn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, part, blocks, C, Rg, gamma, inv, dgamma, dbeta, bw, gsc);
-    if ((C & 3) || (x.ld & 3) || (g.ld & 3) || (y.ld & 3) || (gx.ld & 3) || (gres.p && (gres.ld & 3))) return -22;
     const long total = R * (C >> 2);
     long ab = (total + 255) / 256; if (ab > 16384) ab = 16384; if (ab < 1) ab = 1;
     if (yless) hipLaunchKernelGGL(gbn_bwd_apply_kernel<true>, dim3((int)ab), dim3(256), 0, s, x0, g, y0, gx, gres, act, res_relu, acc_gx, acc_gres, mean, inv, bw, ysc, ysh);

@@ -322,6 +322,8 @@ int ptta_launch_gwgrad(const GView& x, const GView& gy, float* part, float* gw, 
 int ptta_launch_glinear_wgrad(const GView& x, const GView& gy, float* gw, float* gb, hipStream_t s);
 
 int ptta_gbn_part_floats(int C, int npass);
+// the switch combinations the launchers below compute in both directions (they refuse the others with -22 before their first launch)
+bool ptta_gbn_switches_ok(bool has_res, int act, int res_relu, int act_first);
 int ptta_launch_gbn_forward(const GView& x, const GView& res, const GView& y, int npass, int act, float eps, const float* gamma,
                             const float* beta, float* part, float* st, hipStream_t s, int fused_blocks = 0, int act_first = 0,
                             const PttaStatSync* sync = nullptr,

@@ -1,5 +1,5 @@
 // Entry points that take no handle: outlier removal, evaluation metrics, the modulated deformable convolution, and the
-// stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_gconv, ptta_op_conv32_chain).
+// stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_gconv, ptta_op_gbn, ptta_op_conv32_chain).
 #include "msgchn_ctx.h"
 #include "gnet.h"
 
@@ -18,6 +18,16 @@ struct ScratchConvW {
     ScratchConvW(const ScratchConvW&) = delete;
     ScratchConvW& operator=(const ScratchConvW&) = delete;
 };
+
+// ptta_op_gbn's stand-in for the SyncBatchNorm collective: every rank holds the same data, so the sum over `world` ranks is a product
+__global__ void op_scale_f64_kernel(double* buf, long long n, double f) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) buf[i] *= f;
+}
+int op_gbn_exchange(void* user, double* buf, long long count, void* stream) {
+    long long blocks = (count + 255) / 256; if (blocks > 1024) blocks = 1024; if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(op_scale_f64_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, buf, count, (double)*(const int*)user);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
 }  // namespace
 
 extern "C" {
@@ -230,6 +240,66 @@ int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int
             }
     }
     (void)hipFree(wbuf); (void)hipFree(fbuf); (void)hipFree(stat);
+    return rc;
+}
+
+// Stand-alone BatchNorm of the generic engine on fp32 NHWC device views (tests): the launchers of gbn.hip called as GNet::run_bn_fwd /
+// run_bn_bwd call them, with the engine's scratch sizes.  include/ptta.h states the arguments.
+int ptta_op_gbn(const ptta_gbn_args* a, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!a || a->mode < PTTA_GBN_TRAIN || a->mode > PTTA_GBN_BACKWARD) return -22;
+    const bool train = a->mode == PTTA_GBN_TRAIN, eval = a->mode == PTTA_GBN_EVAL, bwd = a->mode == PTTA_GBN_BACKWARD;
+    const int C = a->x.c;
+    auto view_ok = [&](const ptta_gbn_view& v) { return v.p && v.c == C && v.ld >= C && !(v.ld & 3) && !((size_t)v.p & 15); };
+    auto table_ok = [](const void* p) { return p && !((size_t)p & 15); };
+    if (a->b < 1 || a->h < 1 || a->w < 1 || C < 4 || (C & 3) || (a->npass != 1 && a->npass != 2) || (a->b % a->npass) || a->world < 1 ||
+        (a->act != GACT_NONE && a->act != GACT_RELU && a->act != GACT_LRELU && a->act != GACT_ELU) || ((a->act_first | a->res_relu | a->acc_gx | a->acc_gres) & ~1) ||
+        !(a->eps > 0.f)) return -22;
+    if (!view_ok(a->x) || !view_ok(a->y) || !table_ok(a->gamma) || !table_ok(a->st)) return -22;
+    if (eval && a->npass != 1) return -22;
+    if (!bwd) {
+        if ((a->res.p && !view_ok(a->res)) || !table_ok(a->beta)) return -22;
+        // the switch combinations are the launchers' to refuse (before their first launch); the eval affine is launched ahead of the apply
+        // launcher, so that mode asks their predicate here
+        if (eval && !ptta_gbn_switches_ok(a->res.p != nullptr, a->act, a->res_relu, a->act_first)) return -22;
+        if ((a->rm != nullptr) != (a->rv != nullptr) || (eval && !a->rm)) return -22;
+        if (a->rm && (!table_ok(a->rm) || !table_ok(a->rv) || a->repeats < 1 || (a->st_eval && !table_ok(a->st_eval)))) return -22;
+        if (train && a->part_in && a->nblocks_in < 1) return -22;
+    } else {
+        if (!view_ok(a->g) || !view_ok(a->gx) || (a->gres.p && !view_ok(a->gres))) return -22;
+    }
+    auto gv = [&](const ptta_gbn_view& v, int B) { GView o; o.p = v.p; o.B = B; o.H = a->h; o.W = a->w; o.C = v.c; o.ld = v.ld; return o; };
+    const int nb_in = (train && a->part_in) ? a->nblocks_in : 0;
+    size_t npart = (size_t)ptta_gbn_part_floats(C, a->npass);
+    if ((size_t)a->npass * nb_in * 2 * C > npart) npart = (size_t)a->npass * nb_in * 2 * C;       // (a fused BatchNorm owns its partials: GNet Op::part)
+    float *part = nullptr, *bw = nullptr; double* xbuf = nullptr;
+    const long long xcap = (long long)a->npass * 2 * C;
+    int world = a->world, rc = 0;
+    if (!eval && hipMalloc((void**)&part, npart * sizeof(float)) != hipSuccess) rc = -12;
+    if (!rc && bwd && hipMalloc((void**)&bw, (size_t)3 * C * sizeof(float)) != hipSuccess) rc = -12;
+    if (!rc && world > 1 && hipMalloc((void**)&xbuf, (size_t)xcap * sizeof(double)) != hipSuccess) rc = -12;
+    PttaStatSync sy;
+    if (world > 1) { sy.fn = op_gbn_exchange; sy.user = &world; sy.buf = xbuf; sy.cap = (long)xcap; sy.world = world; }
+    if (!rc && nb_in &&
+        hipMemcpyAsync(part, a->part_in, (size_t)a->npass * nb_in * 2 * C * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = -5;
+    if (!rc) {
+        const GView x = gv(a->x, a->b), y = gv(a->y, a->b);
+        GView res; if (!bwd && a->res.p) res = gv(a->res, a->b);
+        if (train)
+            rc = ptta_launch_gbn_forward(x, res, y, a->npass, a->act, a->eps, a->gamma, a->beta, part, a->st, s, nb_in, a->act_first, &sy, a->rm, a->rv,
+                                         a->rm ? a->nbt : nullptr, a->momentum, a->repeats, a->rm ? a->st_eval : nullptr, a->res_relu);
+        else if (eval) {
+            rc = ptta_launch_gbn_eval_affine(a->gamma, a->beta, a->rm, a->rv, a->eps, C, a->st, s);
+            if (!rc) rc = ptta_launch_gbn_apply(x, res, y, 1, a->act, a->st, a->res_relu, s, a->act_first);
+        } else {
+            const int per = a->b / a->npass;
+            GView gres; if (a->gres.p) gres = gv(a->gres, per);
+            rc = ptta_launch_gbn_backward(x, gv(a->g, per), y, gv(a->gx, per), gres, a->npass, a->act, (a->gres.p && a->res_relu) ? 1 : 0, a->acc_gx,
+                                          a->acc_gres, a->gamma, a->st, part, bw, a->dgamma, a->dbeta, s, a->act_first, &sy);
+        }
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    (void)hipFree(part); (void)hipFree(bw); (void)hipFree(xbuf);
     return rc;
 }
 

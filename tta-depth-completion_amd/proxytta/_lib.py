@@ -35,6 +35,17 @@ class Hparams(ctypes.Structure):
                 ('w_cos', c_float), ('max_input_depth', c_float), ('max_predict_depth', c_float)]
 
 
+class GbnView(ctypes.Structure):
+    _fields_ = [('p', c_void_p), ('c', c_int), ('ld', c_int)]
+
+
+class GbnArgs(ctypes.Structure):               # include/ptta.h ptta_gbn_args
+    _fields_ = ([(n, c_int) for n in ('mode', 'b', 'h', 'w', 'npass', 'act', 'act_first', 'res_relu', 'acc_gx', 'acc_gres', 'world',
+                                      'nblocks_in', 'repeats')] + [('eps', c_float), ('momentum', c_float)] +
+                [(n, GbnView) for n in ('x', 'res', 'y', 'g', 'gx', 'gres')] +
+                [(n, c_void_p) for n in ('gamma', 'beta', 'part_in', 'st', 'rm', 'rv', 'nbt', 'st_eval', 'dgamma', 'dbeta')])
+
+
 # every symbol include/ptta.h declares: (name, restype, argtypes)
 _P = c_void_p
 SIGNATURES = [
@@ -104,6 +115,7 @@ SIGNATURES = [
     ('ptta_op_conv32_chain', c_int, [_P] * 6 + [c_int] * 7 + [POINTER(c_float), _P]),
     ('ptta_op_gwgrad', c_int, [_P, _P, _P, _P] + [c_int] * 7 + [POINTER(c_float), _P]),
     ('ptta_op_gconv', c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, _P, _P] + [c_int] * 16 + [POINTER(ctypes.c_double), POINTER(c_int), _P]),
+    ('ptta_op_gbn', c_int, [POINTER(GbnArgs), _P]),
     ('ptta_version', c_int, []),
 ]
 
@@ -148,4 +160,4 @@ def ptr(t):
     return c_void_p(t.data_ptr())
 
 
-__all__ = ['load', 'check', 'ptr', 'Hparams', 'SIGNATURES', 'LIB_PATH', 'byref']
+__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'SIGNATURES', 'LIB_PATH', 'byref']

@@ -543,3 +543,48 @@ def op_gconv(x0, weight, y, x1=None, bias=None, k=3, geom='s1', act='none', accu
         raise RuntimeError('ptta_op_gconv failed (%d)' % rc)
     st = torch.tensor(list(stats), dtype=torch.float64).view(stat_npass, 2, co) if stat_npass else None
     return GCONV_FORMS[form.value], st
+
+
+GBN_MODES = {'train': 0, 'eval': 1, 'backward': 2}
+GBN_ACTS = {'none': 0, 'relu': 1, 'lrelu': 2, 'elu': 4}
+
+
+def op_gbn(mode, x, y, st, gamma, beta=None, res=None, g=None, gx=None, gres=None, npass=1, act='none', act_first=False, res_relu=True,
+           acc_gx=False, acc_gres=False, eps=1e-5, part_in=None, rm=None, rv=None, nbt=None, momentum=0.1, repeats=1, st_eval=None,
+           dgamma=None, dbeta=None, world=1):
+    """Test hook: one BatchNorm of the generic engine (include/ptta.h ptta_op_gbn) on fp32 NHWC device tensors, which may be channel
+    slices of wider tensors (stride(-1) == 1, dense over pixels).  mode 'train' (x, res -> y, st [4, npass, C]; part_in [npass, nblocks,
+    2, C] replaces the statistics pass; rm / rv / nbt / st_eval: a tracked BatchNorm), 'eval' (rm, rv -> st [4, C], y) or 'backward'
+    (x, y over all passes, g / gx / gres over pass 0, st -> gx, gres, dgamma, dbeta).  Everything is written in place; raises
+    RuntimeError naming the return code otherwise."""
+    lib = _lib.load()
+    b, h, w, _ = x.shape
+    a = _lib.GbnArgs()
+
+    def view(t, images):
+        if t is None:
+            return _lib.GbnView(None, 0, 0)
+        n, hh, ww, c = t.shape
+        ld = t.stride(2)
+        assert t.dtype == torch.float32 and (n, hh, ww) == (images, h, w), 'views disagree in size'
+        assert t.stride(3) == 1 and t.stride(1) == w * ld and t.stride(0) == h * w * ld
+        return _lib.GbnView(t.data_ptr(), c, ld)
+
+    def table(t, dtype=torch.float32):
+        if t is None:
+            return None
+        assert t.dtype == dtype and t.is_contiguous()
+        return t.data_ptr()
+    per = b // npass if mode == 'backward' else b
+    a.mode, a.b, a.h, a.w, a.npass = GBN_MODES[mode], b, h, w, int(npass)
+    a.act, a.act_first, a.res_relu, a.acc_gx, a.acc_gres = GBN_ACTS[act], int(bool(act_first)), int(bool(res_relu)), int(bool(acc_gx)), int(bool(acc_gres))
+    a.world, a.repeats, a.eps, a.momentum = int(world), int(repeats), float(eps), float(momentum)
+    a.nblocks_in = int(part_in.shape[1]) if part_in is not None else 0
+    a.x, a.y, a.res = view(x, b), view(y, b), view(res, b)
+    a.g, a.gx, a.gres = view(g, per), view(gx, per), view(gres, per)
+    a.gamma, a.beta, a.part_in, a.st = table(gamma), table(beta), table(part_in), table(st)
+    a.rm, a.rv, a.nbt, a.st_eval = table(rm), table(rv), table(nbt, torch.int64), table(st_eval)
+    a.dgamma, a.dbeta = table(dgamma), table(dbeta)
+    rc = lib.ptta_op_gbn(byref(a), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_gbn failed (%d)' % rc)
