@@ -43,7 +43,7 @@ typedef void* ptta_stream;              /* hipStream_t */
  * ptta_backward ignores its two output pointers (read the 88 gradients with ptta_get_grad) and ptta_adam_step takes
  * NULL gradients (it uses the internal ones); after ptta_set_graph(h, 1) (or PTTA_GRAPH=1) ptta_step and ptta_forward_eval replay
  * captured hipGraphs from their second call on (default off for these handles: measured no faster than plain launches);
- * ptta_profile returns -38.
+ * ptta_profile returns -38.  meta_mode | PTTA_ADAPT_META_ONLY: adapt_parameters('meta') instead (2 adapted tensors; see that flag).
  * PTTA_META_2LAYERS: conv1_rgb_meta = Res_Conv(48, 256) (nlspnmodel_adapt.py:37-45, :1376-1377: conv 48 -> 256, BatchNorm2d + LeakyReLU,
  * conv 256 -> 48 with bias, BatchNorm2d, + its input), fp32 or PTTA_DTYPE_MIXED.  ptta_adapted_count() is 93: the block's seven tensors
  * first, then every other BatchNorm2d; the reference's list has 97 entries because the block's two BatchNorm2d are listed a second time at
@@ -99,7 +99,24 @@ enum { PTTA_NLSPN_LEGACY_OFFSET = 0x100,
         * also matches the heads' three BatchNorm1d: 94 adapted tensors (proj.1, proj_t.1, pred.1 weight/bias appended in
         * module order) instead of 88.  proj / pred feed the detached embedding: their gradients stay zero. */
        PTTA_NLSPN_SYNCBN_ADAPT = 0x200,
-       PTTA_SYNCBN_ADAPT = 0x200 };        /* the same switch for PTTA_BACKBONE_COSTDCNET (see there) */
+       PTTA_SYNCBN_ADAPT = 0x200,          /* the same switch for PTTA_BACKBONE_COSTDCNET (see there) */
+       /* NLSPN, OR-ed into meta_mode: the reference's adapt_mode 'meta' (and 'meta_fix': the same optimiser list, numerically identical in one
+        * process), src/nlspn_model_adapt.py:302-320 -- the method itself: the meta layer alone adapts, every BatchNorm2d is frozen.
+        * ptta_adapted_count() is 2: conv1_rgb_meta.weight, conv1_rgb_meta.bias.  'meta' keeps the loaded running statistics and only sets
+        * track_running_stats = False, so BatchNorm2d behaves differently from 'meta_bn' (which drops the buffers): train-mode passes (the
+        * grad pass and the proxy pass of ptta_forward_train / ptta_step) normalise with batch statistics and write NO buffer; ptta_forward_eval,
+        * the scored forward (src/tta_main.py:729-736), normalises every BatchNorm2d with the LOADED running statistics and loaded gamma / beta:
+        * a constant per-channel affine, which runs in the epilogue of the convolution in front of it (option "eval_bn_fused") -- no statistics,
+        * finalize or apply pass in that forward.  The backward sweep computes no gamma / beta gradient and no weight gradient but the meta
+        * conv's; it still carries the BatchNorm data gradient.  ptta_load_weights keeps running_mean / running_var of every BatchNorm2d; a state
+        * dict without them loads, and the first ptta_forward_eval returns -3 naming the missing tensor.  ptta_debug_tensor reads them back
+        * by their state-dict names ("conv2.0.bn1.running_var", ".weight", ...).  The heads' BatchNorm1d are as in 'meta_bn' (train mode on the
+        * TTA path, their bound buffers updated; no part of the eval forward).
+        * Refused with -38 (ptta_last_error with a NULL handle holds the reason): another backbone; PTTA_META_2LAYERS (the reference freezes the
+        * block's own BatchNorm2d while still listing its gamma / beta: separate work); PTTA_DTYPE_MIXED (no bound measured);
+        * PTTA_NLSPN_SYNCBN_ADAPT.  On such a handle ptta_set_stat_sync, ptta_set_stat_sync_rccl and ptta_set_grad_sync_rccl return -38 and leave it
+        * unchanged (one rank only). */
+       PTTA_ADAPT_META_ONLY = 0x400 };
 
 /* Hyper-parameters of the step.  Reference: src/tta.py:10-160 flags learning_rates,
  * optimizer_betas, optimizer_epsilon, w_weight_decay, w_loss_sparse_depth, w_loss_smoothness,
@@ -400,7 +417,7 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  * handle's streams and drops its captured graphs; the next step re-captures.  Every non-default value is a correct, slower form of
  * the same step, kept as the check of the default (tests/test_gpu_options.py) or taken by the library itself where the default
  * form does not apply (small maps, N > 16, SyncBatchNorm exchange).  Unknown key / value out of range: -22; a key the handle does
- * not have: -38 (the generic engine has "graph" only; PTTA_DTYPE_MIXED handles keep every key but graph / aux_stream / thru / adam_in_wgrad at 1).
+ * not have: -38 (the generic engine has "graph" and, on PTTA_ADAPT_META_ONLY handles, "eval_bn_fused"; PTTA_DTYPE_MIXED handles keep every key but graph / aux_stream / thru / adam_in_wgrad at 1).
  *   key             default  meaning of 0
  *   "graph"         0        (1:) ptta_step / ptta_step_pipelined / ptta_forward_eval replay captured hipGraphs from their second call on.  Default
  *                            since round 5: direct launches on the caller's stream and the handle's own streams -- measured FASTER than replay
@@ -424,6 +441,9 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  *   "stamps"        0        (diagnostic, 1:) fourteen one-thread nodes of the step's and the prefix's graphs write wall_clock64() ticks since
  *                            the step's first node into the debug tensor "stamps" -- where the branches of a replayed step start and end with
  *                            no profiler attached (tools/step_stamps.py, profiles/r05_step_stamps.txt); results unchanged
+ *   "eval_bn_fused" 1        (PTTA_ADAPT_META_ONLY handles only, -38 elsewhere) 0: every BatchNorm2d of the eval forward is its own apply launch
+ *                            from the same affine table (1: in the epilogue of the convolution in front of it).  Bit-identical
+ *                            (tests/test_gpu_nlspn_meta.py): both forms compute fmaf(conv + bias, scale, shift)
  * Read-only keys (ptta_get_option; -22 from ptta_set_option):
  *   "pipelined_active"  1 when ptta_step_pipelined runs as itself on this handle as configured now; 0 when it degrades to ptta_step call by call
  *                       (generic-engine backbones, the dual-corner padded path, a statistics exchange or a gradient communicator bound,
@@ -489,6 +509,18 @@ int ptta_op_gwgrad(const float* x_nhwc, const float* gy_nhwc, float* gw, float* 
 int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y,
                   int co, int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl,
                   int flags, int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, ptta_stream s);
+/* The same hook with the epilogue of the PTTA_ADAPT_META_ONLY eval forward: a BatchNorm2d with constant statistics behind the convolution,
+ *   y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res])
+ * scale / shift [co]: the {scale, shift} rows of an eval affine table (what PTTA_GBN_EVAL leaves in st + 2 co and st + 3 co), 16-byte
+ * aligned; res: the BasicBlock residual, a view [b][hout][wout] of co channels with pixel stride ld_res >= co, added before the activation,
+ * or NULL with ld_res 0.  Bit-identical to ptta_op_gconv with act 0 followed by ptta_op_gbn in mode PTTA_GBN_EVAL with the same activation
+ * (res_relu 1 and act 1 with a residual).  Matrix-core forms only, every geometry: impl 0, c0 and c1 multiples of 8 (PTTA_GCONV_S1) or 16,
+ * act 0 / 1 / 2, no accumulate, no statistics, no bf16x6, no PTTA_GCONV_DGRAD.  -22 BEFORE any launch for anything else, for a NULL or
+ * misaligned scale / shift, and for res without ld_res (or the reverse, or ld_res < co). */
+int ptta_op_gconv_affine(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y,
+                         int co, int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl,
+                         int flags, int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, const float* scale,
+                         const float* shift, const float* res, int ld_res, ptta_stream s);
 /* Test hook: ONE BatchNorm of the generic op-list engine (csrc/gbn.hip: every BatchNorm of NLSPN, CostDCNet and the heads, and the apply /
  * backward launchers of the MSG_CHN 2layers block) on caller-supplied fp32 NHWC device views, launched the way the engine's forward and
  * backward sweeps launch it, with the engine's scratch sizes.  A view is a pointer, its channel count and its pixel stride ld >= c;

@@ -172,6 +172,8 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
     const int co = nf * 32 + i - p.nf0 * 32;          // channel inside the output view
     const bool cok = co < p.Cy;
     const float bias = (cok && p.bias) ? p.bias[co] : 0.f;
+    // the eval affine's two values of this lane's channel, fetched with the bias (GX3Args::scale)
+    const float asc = (cok && p.scale) ? p.scale[co] : 1.f, ash = (cok && p.scale) ? p.shift[co] : 0.f;
     unsigned long long Tpro = 0; STAMP(Tpro);
     for (int q = 0; q < nq; ++q) {
         STAMP(ta);
@@ -275,7 +277,11 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
     // covering eight pixels x 128 contiguous bytes.  Bias / activation / statistics stay in the register layout (per-lane channel);
     // a launch that accumulates adds the old values as float4 after the transpose and activates there.
     const bool sig = p.act == GACT_SIGMOID;
-    const bool wide = !(p.accumulate && (p.stat_part || sig)) && !(p.ldy & 3) && !(p.Cy & 3) && !(((size_t)p.y) & 15);
+    const bool wide = !(p.accumulate && (p.stat_part || sig)) && !(p.ldy & 3) && !(p.Cy & 3) && !(((size_t)p.y) & 15) &&
+                      !(p.res && ((p.ld_res & 3) || (((size_t)p.res) & 15)));
+    // what the float4 stage adds before the activation: the old output (accumulate) or the residual behind the affine
+    const float* const addp = p.accumulate ? p.y : p.res;
+    const int ldadd = p.accumulate ? p.ldy : p.ld_res;
     unsigned long long E1 = 0, E2 = 0, E3 = 0;
     if (wide) {
         lds_barrier();                                    // every wave is done with the tile buffers
@@ -296,8 +302,9 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
             for (int r = 0; r < 16; ++r) {
                 const int px = acc_row(r, h);
                 float v = sig ? acc[rr][r] : acc[rr][r] + bias_w;
+                if (p.scale) v = fmaf(v, asc, ash);
                 if (!p.accumulate) {
-                    v = sig ? v : activate_cheap(v);
+                    v = (sig || p.res) ? v : activate_cheap(v);
                     if (yok && cok && x0 + px < W) { s1 += v; s2 += v * v; }
                 }
                 tw[(rr * 32 + px) * 32 + i] = v;
@@ -311,12 +318,12 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
             // an accumulating launch reads the eight old values FIRST, unconditionally (clamped pixel): one load + s_waitcnt + store per
             // pixel group was eight memory round trips in a row per wave
             float4 old[8];
-            if (p.accumulate) {
+            if (addp) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const int rr = k >> 2, px = (k & 3) * 8 + pl;
                     const int y = min(y0 + 2 * wave + rr, H - 1), x = min(x0 + px, W - 1);
-                    old[k] = *(const float4*)(p.y + (((size_t)b * H + y) * W + x) * p.ldy + cbase);
+                    old[k] = *(const float4*)(addp + (((size_t)b * H + y) * W + x) * ldadd + cbase);
                 }
             }
 #pragma unroll
@@ -326,7 +333,7 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
                 if (y >= H || x >= W) continue;
                 float4 v = *(const float4*)(tw + (rr * 32 + px) * 32 + c4);
                 float* dst = p.y + (((size_t)b * H + y) * W + x) * p.ldy + cbase;
-                if (p.accumulate) {
+                if (addp) {
                     const float4 o = old[k];
                     v.x = activate_cheap(v.x + o.x); v.y = activate_cheap(v.y + o.y); v.z = activate_cheap(v.z + o.z); v.w = activate_cheap(v.w + o.w);
                 }
@@ -345,7 +352,9 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
             if (x >= W) continue;
             float* dst = yrow + (size_t)x * p.ldy;
             float v = acc[rr][r] + bias;
+            if (p.scale) v = fmaf(v, asc, ash);
             if (p.accumulate) v += *dst;
+            if (p.res) v += p.res[(((size_t)b * H + y) * W + x) * p.ld_res + co];
             v = activate(v);
             *dst = v;
             s1 += v; s2 += v * v;
@@ -387,7 +396,9 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
 // NCO = output-channel tiles (of 32) per wave: with two, every A fragment (uncoalesced 32-B pieces of strided pixels, split to
 // bf16 in registers) feeds two weight fragments
 // SIX: bf16x6 for the images below p.six_B (GX3Args), the third operand planes split in registers / streamed like the other two
-template <int MODE, int KS, int KSPLIT, int NCO, bool SIX = false>
+// AFF: the per-channel affine + residual epilogue (GX3Args::scale).  An instantiation of its own: written as a run-time switch it cost the
+// K-split stride-2 forms two registers and with them their third wave per SIMD (136 + 32 -> 138 + 32, compiler's resource usage)
+template <int MODE, int KS, int KSPLIT, int NCO, bool SIX = false, bool AFF = false>
 __global__ __launch_bounds__(256) void gconv_x3_direct_kernel(GX3Args p, int Hin, int Win) {
     constexpr int PAD = KS / 2, KK = KS * KS;
     // stride 2: two output rows per wave, tap-outer / row-inner, so the A loads of both rows are in flight before the
@@ -528,7 +539,9 @@ __global__ __launch_bounds__(256) void gconv_x3_direct_kernel(GX3Args p, int Hin
         const float neg = p.act == GACT_LRELU ? 0.2f * v : (p.act == GACT_RELU ? 0.f : v);
         return v > 0.f ? v : neg;
     };
-    const bool wide = p.act != GACT_SIGMOID && !(p.ldy & 3) && !(p.Cy & 3) && !(((size_t)p.y) & 15);
+    const float* const ares = AFF ? p.res : nullptr;
+    const bool wide = p.act != GACT_SIGMOID && !(p.ldy & 3) && !(p.Cy & 3) && !(((size_t)p.y) & 15) &&
+                      !(ares && ((p.ld_res & 3) || (((size_t)ares) & 15)));
 #pragma unroll
     for (int t = 0; t < NCO; ++t) {
     const int co = (nf + t) * 32 + i - p.nf0 * 32;
@@ -543,6 +556,11 @@ __global__ __launch_bounds__(256) void gconv_x3_direct_kernel(GX3Args p, int Hin
             f32x16 tt;
 #pragma unroll
             for (int r = 0; r < 16; ++r) tt[r] = acc[t][rr][r] + bias;
+            if constexpr (AFF) {                          // the eval affine of this lane's channel (GX3Args::scale), loaded where it is used
+                const float asc = co < p.Cy ? p.scale[co] : 1.f, ash = co < p.Cy ? p.shift[co] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tt[r] = fmaf(tt[r], asc, ash);
+            }
             quad_transpose(tt, lane);
             float* yrow = p.y + ((size_t)b * Hout + y) * Wout * p.ldy + c4;
             bool ok[4]; size_t xo[4]; float4 old[4];
@@ -552,15 +570,18 @@ __global__ __launch_bounds__(256) void gconv_x3_direct_kernel(GX3Args p, int Hin
                 const int x = MODE == 2 ? 2 * xl + xpar : xl;
                 ok[g] = c4 < p.Cy && xl < Wt && x < Wout;
                 xo[g] = (size_t)(ok[g] ? x : 0) * p.ldy;
+                if constexpr (AFF) {                      // the residual behind the affine, added before the activation like an old output
+                    if (ares) old[g] = ok[g] ? *(const float4*)(ares + (((size_t)b * Hout + y) * Wout + x) * p.ld_res + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
             }
-            if (p.accumulate) {
+            if (!AFF && p.accumulate) {                   // (the affine form never accumulates: ptta_gx3_affine_ok)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) old[g] = ok[g] ? *(const float4*)(yrow + xo[g]) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float4 v = make_float4(tt[4 * g], tt[4 * g + 1], tt[4 * g + 2], tt[4 * g + 3]);
-                if (p.accumulate) { v.x += old[g].x; v.y += old[g].y; v.z += old[g].z; v.w += old[g].w; }
+                if (AFF ? ares != nullptr : p.accumulate != 0) { v.x += old[g].x; v.y += old[g].y; v.z += old[g].z; v.w += old[g].w; }
                 v.x = activate_cheap(v.x); v.y = activate_cheap(v.y); v.z = activate_cheap(v.z); v.w = activate_cheap(v.w);
                 if (ok[g]) *(float4*)(yrow + xo[g]) = v;
             }
@@ -581,7 +602,9 @@ __global__ __launch_bounds__(256) void gconv_x3_direct_kernel(GX3Args p, int Hin
             if (MODE == 2 && x >= Wout) continue;         // odd output width: the gradient of a stride-2 conv over an odd-sized map
             float* dst = yrow + (size_t)x * p.ldy;
             float v = acc[t][rr][r] + bias;
-            if (p.accumulate) v += *dst;
+            if constexpr (AFF) v = fmaf(v, p.scale[co], p.shift[co]);
+            if (!AFF && p.accumulate) v += *dst;
+            if (ares) v += ares[(((size_t)b * Hout + y) * Wout + x) * p.ld_res + co];
             *dst = activate(v);
         }
     }
@@ -914,7 +937,7 @@ int ptta_gconv_x3_tiles(int B, int H, int W) { return B * ((W + 31) / 32) * ((H 
 
 int ptta_launch_gconv_x3(const GX3Args& a, int ks, hipStream_t s) {
     if ((a.C0 & 7) || (a.C1 & 7) || (a.ld0 & 3) || (a.ld1 & 3)) return -22;        // channel counts: multiples of 8
-    if (a.nchunks != (a.C0 + 31) / 32 + (a.C1 + 31) / 32) return -22;
+    if (a.nchunks != (a.C0 + 31) / 32 + (a.C1 + 31) / 32 || !ptta_gx3_affine_ok(a)) return -22;
     const long tiles = (long)a.B * ((a.W + 31) / 32) * ((a.H + GX_TH - 1) / GX_TH);
     const long blocks = tiles * a.nnf;
     if (blocks < 1 || blocks > 0x7fffffffL) return -22;
@@ -953,7 +976,7 @@ int ptta_gconv_x3_strided_form(const GX3Args& a, int ks, int mode, int win, long
 // mode 1: stride-2 convolution (a.H/a.W = output size, input = hin x win); mode 2: stride-2 transposed convolution
 int ptta_launch_gconv_x3_strided(const GX3Args& a, int ks, int mode, int hin, int win, hipStream_t s) {
     if ((a.C0 & 15) || (a.C1 & 15) || (a.ld0 & 3) || (a.ld1 & 3) || (ks != 1 && ks != 3) || (mode != 1 && mode != 2)) return -22;
-    if (a.nchunks != (a.C0 + 31) / 32 + (a.C1 + 31) / 32) return -22;
+    if (a.nchunks != (a.C0 + 31) / 32 + (a.C1 + 31) / 32 || !ptta_gx3_affine_ok(a)) return -22;
     long nitems = 0;
     const int form = ptta_gconv_x3_strided_form(a, ks, mode, win, &nitems);
     const bool split = form == GX3_FORM_KSPLIT;
@@ -962,6 +985,17 @@ int ptta_launch_gconv_x3_strided(const GX3Args& a, int ks, int mode, int hin, in
     const long blocks = (split ? nitems : (nitems + 3) / 4) * ngrp;
     if (blocks < 1 || blocks > 0x7fffffffL) return -22;
     if (a.six_B > 0 && !a.wl2) return -22;
+    if (a.scale) {                         // the affine epilogue's instantiations (bf16x3 only: the eval forward of NLSPN's meta-only mode)
+        if (a.six_B > 0) return -22;
+#define LA_(M, K) do { if (nco == 2) hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 1, 2, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); \
+                      else if (split) hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 4, 1, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); \
+                      else hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 1, 1, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); } while (0)
+        if (mode == 1) { if (ks == 3) LA_(1, 3); else LA_(1, 1); }
+        else { if (ks == 3) LA_(2, 3); else LA_(2, 1); }
+#undef LA_
+        PTTA_CHECK_LAUNCH();
+        return 0;
+    }
 #define L__(M, K, S) do { if (nco == 2) hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 1, 2, S>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); \
                       else if (split) hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 4, 1, S>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); \
                       else hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 1, 1, S>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); } while (0)

@@ -92,6 +92,11 @@ struct Op {
     float *rm = nullptr, *rv = nullptr; long long* nbt = nullptr;
     float *rm_own = nullptr, *rv_own = nullptr;   // BatchNorm2d (not tracked): the LOADED running statistics, used by the stage-2 head trainer only
     bool has_running = false;
+    bool has_rm = false, has_rv = false;   // which of the two buffers a load() brought (meta-only mode: the eval forward names a missing one)
+    // meta-only mode (GNet::meta_only), eval forward: this BN's constant affine runs in the epilogue of the CONV op aff_from, at this BN's
+    // place in the op list (the BasicBlock residual exists by then); that CONV op (aff_fused) is skipped at its own place
+    int aff_from = -1;
+    bool aff_fused = false;
     bool no_dx = false;               // (CONV) no data gradient into the source although it has a gradient buffer (head trainer: detached input)
     float* st_eval = nullptr;         // tracked: eval-mode affine [mean, inv, scale, shift][C] of the running statistics
     mutable bool st_eval_valid = false;   // written by the last training forward's finalize (or an eval forward); cleared by every load()
@@ -193,6 +198,14 @@ struct GNet {
     // bn_prepare is set, BN ops that are not `tracked` (= the BatchNorm2d's) normalise every pass with their LOADED running statistics;
     // 2 (the SyncBatchNorm form, ptta_head_set_form): the `tracked` ones too, from their bound running statistics, which stay untouched
     int bn_prepare = 0;
+    // adapt_mode 'meta' / 'meta_fix' of the reference (src/nlspn_model_adapt.py:302-320; include/ptta.h PTTA_ADAPT_META_ONLY): the meta conv
+    // alone adapts, every BatchNorm2d keeps its loaded gamma / beta and running statistics.  Train-mode passes normalise with batch statistics
+    // and write no buffer (track_running_stats = False); the eval forward normalises with the loaded running statistics -- a constant
+    // per-channel affine (Op::st_eval, built once per load by prepare_eval_affines) that runs in the producing convolution's epilogue
+    // (eval_bn_fused, option "eval_bn_fused") or as a separate gbn_apply; no statistics pass either way
+    int meta_only = 0, eval_bn_fused = 1;
+    void plan_eval_affine();
+    int prepare_eval_affines(hipStream_t s);
     PttaStatSync stat_sync;               // SyncBatchNorm exchange (ptta_set_stat_sync); world == 1: off
     void* grad_comm = nullptr;            // RCCL communicator of the gradient all-reduce inside step() (ptta_set_grad_sync_rccl)
 
@@ -440,7 +453,7 @@ struct GNet {
     // ---- execution -------------------------------------------------------------------------------------------------
     const float* bn_gamma(const Op& o) { return o.ad_g >= 0 ? adapted[o.ad_g].p : frozen_bn[o.bname].first; }
     const float* bn_beta(const Op& o) { return o.ad_beta >= 0 ? adapted[o.ad_beta].p : frozen_bn[o.bname].second; }
-    int run_conv_fwd(const Op& o, bool train, hipStream_t s);
+    int run_conv_fwd(const Op& o, bool train, hipStream_t s, const Op* aff = nullptr);      // aff: the BN op whose eval affine rides in the epilogue
     int run_bn_fwd(const Op& o, bool train, hipStream_t s);
     int run_conv_bwd(const Op& o, hipStream_t s);
     int run_bn_bwd(const Op& o, hipStream_t s);
@@ -449,6 +462,7 @@ struct GNet {
         for (const Op& o : ops) {
             if (limit >= 0 && idx++ >= limit) break;
             if (o.train_only && !train) continue;
+            if (o.aff_fused && !train && meta_only && eval_bn_fused) continue;       // runs at its BatchNorm's place (run_bn_fwd)
             const int rc = o.kind == gnet::K_CONV ? run_conv_fwd(o, train, s) : (o.kind == gnet::K_BN ? run_bn_fwd(o, train, s) : o.ffwd(train, s));
             if (rc) return rc;
         }

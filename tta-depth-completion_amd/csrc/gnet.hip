@@ -39,6 +39,7 @@ int GNet::load(const char* name_c, const void* tensor_, const int64_t* shape, in
             if (o.kind == K_BN && !o.tracked && o.bname == base && o.rm_own && ndim == 1 && shape[0] == T[o.x[0]].C) {
                 NCHK(hipMemcpyAsync(leaf == "running_mean" ? o.rm_own : o.rv_own, src, (size_t)shape[0] * sizeof(float), hipMemcpyDeviceToDevice, s));
                 o.has_running = true;
+                (leaf == "running_mean" ? o.has_rm : o.has_rv) = true;
             }
     }
     auto it = convs.find(base);
@@ -71,14 +72,50 @@ int GNet::load(const char* name_c, const void* tensor_, const int64_t* shape, in
 }
 
 // ---- execution ---------------------------------------------------------------------------------------------------------
-int GNet::run_conv_fwd(const Op& o, bool train, hipStream_t s) {
+// meta-only mode: which eval-forward BatchNorm2d ride in their convolution's epilogue.  The BN must read the raw output of a matrix-core
+// convolution without an activation of its own, over the same passes, in one of the switch combinations the epilogue computes; and because
+// the fused launch runs at the BN's place in the list, nothing between the two may read that raw output or write one of the convolution's sources.
+void GNet::plan_eval_affine() {
+    for (int i = 0; i < (int)ops.size(); ++i) {
+        Op& b = ops[i];
+        if (b.kind != K_BN || b.tracked || b.train_only || b.act_first || (b.res >= 0 && !b.res_relu) || b.rH > 0) continue;
+        if (b.act != GACT_NONE && b.act != GACT_RELU && b.act != GACT_LRELU) continue;
+        int k = i - 1;
+        while (k >= 0 && !(ops[k].kind == K_CONV && ops[k].y == b.x[0])) --k;
+        if (k < 0) continue;
+        const Op& c = ops[k];
+        if (!convs[c.wname].mf || c.act != GACT_NONE || c.yw != b.xw[0] || c.train_only || c.rH > 0 || convs[c.wname].vcol) continue;
+        bool clean = true;
+        for (int j = k + 1; j < i && clean; ++j) {
+            const Op& m = ops[j];
+            if (m.kind == K_FUNC) clean = false;
+            else if (m.x[0] == b.x[0] || (m.kind == K_CONV && m.nsrc == 2 && m.x[1] == b.x[0]) || (m.kind == K_BN && m.res == b.x[0])) clean = false;
+            else for (int sidx = 0; sidx < c.nsrc; ++sidx) if (m.y == c.x[sidx]) clean = false;
+        }
+        if (!clean) continue;
+        b.aff_from = k; ops[k].aff_fused = true;
+    }
+}
+// the eval affine of every BatchNorm2d from its LOADED buffers (gbn_eval_affine_kernel: PTTA_GBN_EVAL's finalize); once per load()
+int GNet::prepare_eval_affines(hipStream_t s) {
+    for (const Op& o : ops) {
+        if (o.kind != K_BN || o.tracked || o.train_only || o.st_eval_valid) continue;
+        if (!o.has_rm || !o.has_rv)
+            return fail(o.bname + (o.has_rm ? ".running_var" : ".running_mean") + " not loaded: this handle's eval forward normalises with the loaded running statistics (ptta_load_weights)", -3);
+        if (ptta_launch_gbn_eval_affine(bn_gamma(o), bn_beta(o), o.rm_own, o.rv_own, BN_EPS, T[o.x[0]].C, o.st_eval, s)) return fail("batch-norm " + o.bname + " (eval affine) launch failed", -5);
+        o.st_eval_valid = true;
+    }
+    return 0;
+}
+
+int GNet::run_conv_fwd(const Op& o, bool train, hipStream_t s, const Op* aff) {
     const bool ad = o.ad_w >= 0;
     const GConvW& cw = convs[o.wname];
     if (!ad && !cw.loaded) return fail("weights of " + o.wname + " not loaded (ptta_load_weights)", -3);
     const float* bias = ad ? (o.ad_b >= 0 ? adapted[o.ad_b].p : nullptr) : (cw.has_bias ? cw.bias : nullptr);
     if (cw.mf) {
         GX3Args a;
-        GView x0 = view(o.x[0], o.xw[0], train), y = view(o.y, o.yw, train);
+        GView x0 = view(o.x[0], o.xw[0], train), y = view(aff ? aff->y : o.y, o.yw, train);
         review(x0, o.rH, o.rW); review(y, o.rH, o.rW);
         a.x0 = x0.p; a.C0 = x0.C; a.ld0 = x0.ld;
         if (o.nsrc == 2) { const GView x1 = view(o.x[1], o.xw[1], train); a.x1 = x1.p; a.C1 = x1.C; a.ld1 = x1.ld; }
@@ -90,7 +127,12 @@ int GNet::run_conv_fwd(const Op& o, bool train, hipStream_t s) {
             a.wl2 = (const uint4*)cw.ff_l2; a.six_B = (o.yw == W_BOTH && train) ? y.B / 2 : y.B;
         }
         if ((mixed & 1) && train && o.yw != W_GRAD) a.x1_from_B = o.yw == W_BOTH ? y.B / 2 : 0;     // the proxy frames' products: one MFMA
-        if (o.stat_to >= 0 && (train || !ops[o.stat_to].tracked) && !(bn_prepare && !ops[o.stat_to].tracked) && !bn_eval_in_train(ops[o.stat_to])) {
+        if (aff) {          // y = act(fmaf(conv + bias, scale, shift) [+ res]): the BN's activation, or the BasicBlock's ReLU behind the sum
+            a.scale = aff->st_eval + 2 * y.C; a.shift = aff->st_eval + 3 * y.C;
+            a.act = aff->res >= 0 ? GACT_RELU : aff->act;
+            if (aff->res >= 0) { const GView r = view(aff->res, aff->xw[0], train); a.res = r.p; a.ld_res = r.ld; }
+        }
+        if (o.stat_to >= 0 && !(meta_only && !train) && (train || !ops[o.stat_to].tracked) && !(bn_prepare && !ops[o.stat_to].tracked) && !bn_eval_in_train(ops[o.stat_to])) {
             a.stat_part = ops[o.stat_to].part; a.stat_C = y.C; a.stat_npass = (o.yw == W_BOTH && train) ? 2 : 1;
         }
         int rc;
@@ -117,6 +159,12 @@ int GNet::run_bn_fwd(const Op& o, bool train, hipStream_t s) {
     GView x = view(o.x[0], o.xw[0], train), y = view(o.y, o.yw, train);
     GView res; if (o.res >= 0) res = view(o.res, o.xw[0], train);
     const int npass = (o.xw[0] == W_BOTH && train) ? 2 : 1;
+    if (meta_only && !train && !o.tracked && !bn_prepare) { // meta-only mode, eval forward: the constant affine of the loaded running statistics
+        if (!o.st_eval_valid) return fail("eval affine of " + o.bname + " not prepared", -3);
+        if (eval_bn_fused && o.aff_from >= 0) return run_conv_fwd(ops[o.aff_from], false, s, &o);
+        if (ptta_launch_gbn_apply(x, res, y, 1, o.act, o.st_eval, o.res_relu ? 1 : 0, s, o.act_first ? 1 : 0)) return fail("batch-norm " + o.bname + " (eval) launch failed", -5);
+        return 0;
+    }
     if (bn_prepare && !o.tracked) {                         // stage-2 head trainer: a BatchNorm2d in eval mode, every pass from the loaded running statistics
         if (!o.has_running) return fail("running statistics of " + o.bname + " not loaded (the stage-2 head trainer evaluates BatchNorm2d from them)", -3);
         if (ptta_launch_gbn_eval_affine(bn_gamma(o), bn_beta(o), o.rm_own, o.rv_own, BN_EPS, x.C, o.st_eval, s)) return fail("batch-norm " + o.bname + " (prepare) launch failed", -5);
@@ -280,6 +328,7 @@ int GNet::replay(int key, std::function<int(hipStream_t)> body, hipStream_t s) {
 }
 int GNet::forward_eval(const float* image, const float* sparse, float* depth_out, hipStream_t s) {
     int rc;
+    if (meta_only) { rc = prepare_eval_affines(s); if (rc) return rc; }       // before any capture: after a load() only
     if (graph_ok() && eager_eval_done) {
         rc = stage_inputs(image, nullptr, sparse, nullptr, s);
         if (rc) return rc;
@@ -366,7 +415,19 @@ int GNet::debug_tensor(const char* name, float* dst, int64_t capacity, int64_t* 
     if (nm == "depth") { src = depth; n = (long)Nu * Hu * Wu; }
     else {
         auto it = tid.find(nm);
-        if (it == tid.end()) { const int rc = debug_extra(nm, &src, &n); if (rc) return rc; }
+        // a BatchNorm2d's loaded buffers and affine parameters, by their state-dict names
+        if (it == tid.end() && !grad) {
+            const size_t dot = nm.rfind('.');
+            const std::string base = dot == std::string::npos ? nm : nm.substr(0, dot), leaf = dot == std::string::npos ? "" : nm.substr(dot + 1);
+            for (const Op& o : ops) {
+                if (o.kind != K_BN || o.tracked || o.bname != base || !o.rm_own) continue;
+                if (leaf == "running_mean") src = o.rm_own; else if (leaf == "running_var") src = o.rv_own;
+                else if (leaf == "weight") src = bn_gamma(o); else if (leaf == "bias") src = bn_beta(o);
+                if (src) { n = T[o.x[0]].C; break; }
+            }
+        }
+        if (src) {}
+        else if (it == tid.end()) { const int rc = debug_extra(nm, &src, &n); if (rc) return rc; }
         else {
             const Tn& t = T[it->second];
             if (t.ld != t.C) return fail("debug tensor " + nm + " is a strided slice", -22);

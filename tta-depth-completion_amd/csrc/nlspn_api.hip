@@ -4,6 +4,9 @@
 // adapt (88 tensors / 40,048 values), every BatchNorm2d normalises with batch statistics in train and eval mode.
 // 2layers (prepare_mode 'meta_selfsup_seq_2layers_ema'): conv1_rgb_meta is Res_Conv(48, 256) (nlspnmodel_adapt.py:37-45, :1376-1377),
 // conv 48 -> 256 - BN - LeakyReLU(0.2) - conv 256 -> 48 (+ bias) - BN, + its input: 93 tensors, the block's two BatchNorm2d listed twice (97 entries).
+// meta-only (PTTA_ADAPT_META_ONLY; adapt_parameters('meta') / ('meta_fix'), src/nlspn_model_adapt.py:302-320): conv1_rgb_meta's weight and bias
+// alone adapt; every BatchNorm2d keeps its loaded gamma / beta and its running statistics (track_running_stats = False: batch statistics in
+// train mode, no buffer written; the loaded running statistics in the scored eval forward, src/tta_main.py:729-736) -- gnet.h GNet::meta_only.
 //
 // The network is a flat op list built once per handle ("program"): CONV (one or two channel-concatenated
 // sources, so torch.cat never materialises), BN (+activation, + residual add of a BasicBlock), then the fused
@@ -67,6 +70,7 @@ struct nlspn_engine : GNet {
     int t_img = -1, t_sd = -1, t_pred = -1, t_oa = -1, t_conf = -1, t_fe6 = -1;
     float *off9 = nullptr, *aff9 = nullptr, *goff9 = nullptr, *gaff9 = nullptr, *feats = nullptr, *gy = nullptr, *gping = nullptr;
     int legacy = 0, heads_adapted = 0, meta2 = 0;
+    bool fz = false;                   // meta-only mode: every BatchNorm2d frozen (gamma / beta loaded, not adapted)
     int enc_ops_end = 0;               // ops [0, enc_ops_end) = conv1 .. conv6: what the stage-2 head trainer runs of the backbone
 
     static int half(int v) { return (v + 1) / 2; }                 // 3x3 stride 2 padding 1: ceil
@@ -127,21 +131,21 @@ struct nlspn_engine : GNet {
                 const int r1 = tensor(P + ".r1", N2, ho, wo, C, true), a1 = tensor(P + ".a1", N2, ho, wo, C, true);
                 const int r2 = tensor(P + ".r2", N2, ho, wo, C, true), out = tensor(P + ".out", N2, ho, wo, C, true);
                 conv(P + ".conv1", cur, -1, r1, 3, stride, 0, GACT_NONE, W_BOTH, W_BOTH);
-                bn(P + ".bn1", r1, a1, -1, GACT_RELU, W_BOTH);
+                bn(P + ".bn1", r1, a1, -1, GACT_RELU, W_BOTH, fz);
                 conv(P + ".conv2", a1, -1, r2, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH);
                 int idt = cur;
                 if (stride != 1 || T[cur].C != C) {
                     const int rd = tensor(P + ".rd", N2, ho, wo, C, true), d = tensor(P + ".d", N2, ho, wo, C, true);
                     // module order inside the block: conv1, bn1, conv2, bn2, downsample (parameter order of the reference)
-                    bn(P + ".bn2", r2, out, d, GACT_NONE, W_BOTH);
+                    bn(P + ".bn2", r2, out, d, GACT_NONE, W_BOTH, fz);
                     Op bn2 = ops.back(); ops.pop_back();
                     conv(P + ".downsample.0", cur, -1, rd, 1, stride, 0, GACT_NONE, W_BOTH, W_BOTH);
-                    bn(P + ".downsample.1", rd, d, -1, GACT_NONE, W_BOTH);
+                    bn(P + ".downsample.1", rd, d, -1, GACT_NONE, W_BOTH, fz);
                     ops.push_back(bn2);
                     if (bn2.fused_from >= 0) ops[bn2.fused_from].stat_to = (int)ops.size() - 1;     // bn2 moved behind the downsample ops
                     idt = d;
                 } else {
-                    bn(P + ".bn2", r2, out, idt, GACT_NONE, W_BOTH);
+                    bn(P + ".bn2", r2, out, idt, GACT_NONE, W_BOTH, fz);
                 }
                 cur = out; hh = ho; ww = wo;
             }
@@ -150,7 +154,7 @@ struct nlspn_engine : GNet {
         {   // conv6 = conv_bn_relu(512, 512, 3, stride 2) (:409)
             const int r = tensor("conv6.r", N2, H16, W16, 512, true), o = tensor("fe6", N2, H16, W16, 512, true);
             conv("conv6.0", fe[5], -1, r, 3, 2, 0, GACT_NONE, W_BOTH, W_BOTH);
-            bn("conv6.1", r, o, -1, GACT_LRELU, W_BOTH);
+            bn("conv6.1", r, o, -1, GACT_LRELU, W_BOTH, fz);
             fe[6] = o; t_fe6 = o;
         }
         enc_ops_end = (int)ops.size();
@@ -162,7 +166,7 @@ struct nlspn_engine : GNet {
             const int hf = 2 * hin, wf = 2 * win;
             const int r = tensor(std::string(name) + ".r", N, hf, wf, cout, true), o = tensor(std::string(name) + ".o", N, hf, wf, cout, true);
             conv(std::string(name) + ".0", a, b, r, 3, 2, 1, GACT_NONE, W_GRAD, W_GRAD);
-            bn(std::string(name) + ".1", r, o, -1, GACT_LRELU, W_GRAD);
+            bn(std::string(name) + ".1", r, o, -1, GACT_LRELU, W_GRAD, fz);
             if (hf == h && wf == w) return o;
             const int oc = tensor(std::string(name) + ".crop", N, h, w, cout, true);
             const int oi = func(nullptr, nullptr, o);
@@ -186,7 +190,7 @@ struct nlspn_engine : GNet {
         auto head1 = [&](const char* name, int cout) {
             const int r = tensor(std::string(name) + ".r", N, H, W, cout, true), o = tensor(std::string(name) + ".o", N, H, W, cout, true);
             conv(std::string(name) + ".0", fd2, fe[2], r, 3, 1, 0, GACT_NONE, W_GRAD, W_GRAD);
-            bn(std::string(name) + ".1", r, o, -1, GACT_LRELU, W_GRAD);
+            bn(std::string(name) + ".1", r, o, -1, GACT_LRELU, W_GRAD, fz);
             return o;
         };
         // module order: id_dec1, id_dec0, gd_dec1, gd_dec0, cf_dec1, cf_dec0 (:428-452)
@@ -220,6 +224,7 @@ struct nlspn_engine : GNet {
         tid["emb"] = t_emb;
 
         plan_backward({t_pred, t_oa, t_conf, t_ref});           // written by the propagation / loss gradients
+        if (meta_only) plan_eval_affine();
         // ---- remaining workspace ----
         const long P = (long)H * W;
         off9 = falloc((size_t)N * P * 18); aff9 = falloc((size_t)N * P * 9);
@@ -242,7 +247,7 @@ struct nlspn_engine : GNet {
                     if (leaf == "running_mean") o.rm = (float*)src; else if (leaf == "running_var") o.rv = (float*)src; else o.nbt = (long long*)src;
                     return 0;
                 }
-            return 0;                    // BatchNorm2d: dropped by adapt_parameters('meta_bn')
+            return 0;                    // BatchNorm2d: dropped by adapt_parameters('meta_bn'); kept by GNet::load for the head trainer and the meta-only mode
         }
         if (name == "prop_layer.aff_scale_const") { NCHK(hipMemcpyAsync(S, src, sizeof(float), hipMemcpyDeviceToDevice, s)); return 0; }
         if (name == "prop_layer.w" || name == "prop_layer.b" || name == "prop_layer.w_conf") return 0;   // constants ones / zero (nlspnmodel_adapt.py:239-247)
@@ -336,6 +341,7 @@ GNet* nlspn_create(int n, int h, int w, const ptta_hparams* hp, int legacy_offse
     nlspn_engine* e = new nlspn_engine();
     e->N = e->Nu = n; e->H = e->Hu = h; e->W = e->Wu = w; e->hp = *hp; e->legacy = (legacy_offset & 1) ? 1 : 0; e->heads_adapted = (legacy_offset & 2) ? 1 : 0;
     e->meta2 = (legacy_offset & 4) ? 1 : 0;
+    e->meta_only = (legacy_offset & 8) ? 1 : 0; e->fz = e->meta_only != 0;
     const PttaCreateEnv env = ptta_create_env();
     e->naive = env.naive;          // direct fp32 kernels everywhere (validation)
     e->x6 = 0;                     // (third operand plane: off -- matrix-core bound, parity holds without)

@@ -23,7 +23,14 @@ extern "C" {
 
 int ptta_version(void) { return PTTA_ABI_VERSION; }
 
-const char* ptta_last_error(ptta_handle h) { return h ? (h->nl && h->err.empty() ? h->nl->err.c_str() : h->err.c_str()) : "null handle"; }
+// why the calling thread's last ptta_create refused a configuration (there is no handle to ask then): ptta_last_error(NULL)
+static thread_local std::string g_create_err;
+static int create_refused(const std::string& why) { g_create_err = why; return -38; }
+
+const char* ptta_last_error(ptta_handle h) {
+    if (!h) return g_create_err.empty() ? "null handle" : g_create_err.c_str();
+    return h->nl && h->err.empty() ? h->nl->err.c_str() : h->err.c_str();
+}
 
 // a created generic engine (NLSPN, CostDCNet) as a handle: every entry point forwards to it
 static int wrap_gnet(ptta_handle* out, GNet* e, int rc, int gmix, int n, int height, int width, const ptta_hparams* hp) {
@@ -38,6 +45,14 @@ static int wrap_gnet(ptta_handle* out, GNet* e, int rc, int gmix, int n, int hei
 int ptta_create(ptta_handle* out, int backbone_id, int meta_mode, int n, int height, int width, int dtype, const ptta_hparams* hp) {
     if (!out) return -1;
     *out = nullptr;
+    g_create_err.clear();
+    // the meta-only adapted list is built for NLSPN's 1layer meta conv in fp32 (include/ptta.h PTTA_ADAPT_META_ONLY); refused before anything is allocated
+    if (meta_mode & PTTA_ADAPT_META_ONLY) {
+        if (backbone_id != PTTA_BACKBONE_NLSPN) return create_refused("PTTA_ADAPT_META_ONLY: only the NLSPN adapter has adapt_mode 'meta'");
+        if ((meta_mode & 0xff) == PTTA_META_2LAYERS) return create_refused("PTTA_ADAPT_META_ONLY with PTTA_META_2LAYERS: the block's own BatchNorm2d under 'meta' is not built");
+        if ((dtype & 0xff) == PTTA_DTYPE_MIXED) return create_refused("PTTA_ADAPT_META_ONLY with PTTA_DTYPE_MIXED: no bound has been measured for it");
+        if (meta_mode & PTTA_NLSPN_SYNCBN_ADAPT) return create_refused("PTTA_ADAPT_META_ONLY with PTTA_NLSPN_SYNCBN_ADAPT: the SyncBatchNorm form of this mode is not offered");
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return -19;          // no HIP device: fail loudly
     // generic engine (NLSPN, CostDCNet): PTTA_DTYPE_MIXED = fp32 storage, single-MFMA products for the proxy frames and the data gradients
@@ -48,12 +63,12 @@ int ptta_create(ptta_handle* out, int backbone_id, int meta_mode, int n, int hei
     if (backbone_id != PTTA_BACKBONE_MSG_CHN && (dtype & 0xff) == PTTA_DTYPE_MIXED) dtype = PTTA_DTYPE_F32;
     if (backbone_id == PTTA_BACKBONE_NLSPN) {
         // 2layers: the Res_Conv(48, 256) block (nlspn_api.hip), fp32 and mixed; not with the adapted set of the DDP run (its repeat structure differs)
-        const int meta = meta_mode & ~(PTTA_NLSPN_LEGACY_OFFSET | PTTA_NLSPN_SYNCBN_ADAPT);
+        const int meta = meta_mode & ~(PTTA_NLSPN_LEGACY_OFFSET | PTTA_NLSPN_SYNCBN_ADAPT | PTTA_ADAPT_META_ONLY);
         if ((meta != PTTA_META_1LAYER && meta != PTTA_META_2LAYERS) || dtype != PTTA_DTYPE_F32) return -38;
         if (meta == PTTA_META_2LAYERS && (meta_mode & PTTA_NLSPN_SYNCBN_ADAPT)) return -38;
         int rc = 0;
         GNet* e = nlspn_create(n, height, width, hp, ((meta_mode & PTTA_NLSPN_LEGACY_OFFSET) ? 1 : 0) | ((meta_mode & PTTA_NLSPN_SYNCBN_ADAPT) ? 2 : 0) |
-                               (meta == PTTA_META_2LAYERS ? 4 : 0), &rc);
+                               (meta == PTTA_META_2LAYERS ? 4 : 0) | ((meta_mode & PTTA_ADAPT_META_ONLY) ? 8 : 0), &rc);
         return wrap_gnet(out, e, rc, gmix, n, height, width, hp);
     }
     if (backbone_id == PTTA_BACKBONE_COSTDCNET) {
@@ -368,6 +383,7 @@ int ptta_set_image_norm(ptta_handle c, float divisor, const float* mean, const f
 // step's stream and are captured like any kernel (RCCL) -- otherwise they are host-driven and the step cannot be replayed.  Either way the
 // second stream is given up while an exchange is on (collectives of one communicator are kept in one stream order).
 static int set_stat_sync(ptta_ctx* c, const PttaStatSync& sy, bool on, bool keeps_graph) {
+    if (c->nl && c->nl->meta_only) { c->err.clear(); return c->nl->fail("the SyncBatchNorm form of the meta-only adaptation mode is not offered (PTTA_ADAPT_META_ONLY)", -38); }
     if (c->nl) { c->err.clear(); c->nl->drop_graphs(); c->nl->stat_sync = sy; return 0; }
     if (on && c->meta_mode == PTTA_META_2LAYERS && !c->m2.generic) return c->fail("SyncBatchNorm needs the default arithmetic for the 2layers meta layer", -38);
     c->stat_sync = sy;
@@ -404,6 +420,7 @@ int ptta_set_stat_sync_rccl(ptta_handle c, void* comm, double* exchange_buf, int
 // ncclAllReduce enqueued on the step's stream (captured into the hipGraph).  comm == NULL: off.
 int ptta_set_grad_sync_rccl(ptta_handle c, void* comm) {
     if (!c) return -1;
+    if (c->nl && c->nl->meta_only) { c->err.clear(); return c->nl->fail("no gradient exchange in the meta-only adaptation mode: more than one rank is not offered (PTTA_ADAPT_META_ONLY)", -38); }
     if (c->nl) { c->nl->drop_graphs(); c->nl->grad_comm = comm; return 0; }
     c->grad_comm = comm;
     c->drop_graphs();
@@ -431,7 +448,15 @@ int ptta_set_option(ptta_handle c, const char* key, int value) {
     if (!c || !key) return -1;
     const std::string k(key);
     if (k == "graph") return ptta_set_graph(c, value);
-    if (c->nl) return -38;                         // the generic engine has the one switch
+    if (k == "eval_bn_fused") {                    // meta-only NLSPN handles: the eval BatchNorm2d in the convolution epilogue (1) or as its own launch (0)
+        if (!c->nl || !c->nl->meta_only) return c->nl ? (c->err.clear(), c->nl->fail("ptta_set_option: 'eval_bn_fused' belongs to PTTA_ADAPT_META_ONLY handles", -38))
+                                                      : c->fail("ptta_set_option: 'eval_bn_fused' belongs to PTTA_ADAPT_META_ONLY handles", -38);
+        c->err.clear();
+        if (value < 0 || value > 1) return c->nl->fail("ptta_set_option: value out of range for 'eval_bn_fused'", -22);
+        if (c->nl->eval_bn_fused != value) { c->nl->drop_graphs(); c->nl->eval_bn_fused = value; }
+        return 0;
+    }
+    if (c->nl) return -38;                         // the generic engine has the one switch besides
     const Option* o = find_option(k);
     if (!o) return c->fail("ptta_set_option: unknown key '" + k + "'", -22);
     int* f = &(c->*(o->member));
@@ -456,6 +481,7 @@ int ptta_get_option(ptta_handle c, const char* key, int* value) {
     // read-only: 1 when the step takes the two-stream `thru` schedule (loss gradient from the valid-weight partials), as far as it can be known
     // without the caller's stream (the second stream is created on first use)
     if (k == "thru_active") { *value = c->nl ? 0 : (c->thru && c->cos_grad_fused && heads_v2_on(c) && c->use_aux); return 0; }
+    if (k == "eval_bn_fused") { if (!c->nl || !c->nl->meta_only) return -38; *value = c->nl->eval_bn_fused; return 0; }
     if (c->nl) { if (k != "graph") return -38; *value = c->nl->use_graph; return 0; }
     if (k == "graph") { *value = c->use_graph; return 0; }
     const Option* o = find_option(k);

@@ -370,7 +370,18 @@ struct GX3Args {
     // ... with the WEIGHT operand kept as hi + lo (two MFMAs: a_hi w_lo, a_hi w_hi): the data gradients.  A bf16-rounded weight is a systematic
     // error of the gradient's direction (conv32.hip mma_step W2), a rounded gradient value is noise
     int x1_w2 = 0;
+    // optional per-channel affine behind the convolution (a BatchNorm2d evaluated from constant statistics: the {scale, shift} rows of its
+    // st_eval table, indexed by the channel inside the output view) and the BasicBlock residual (pixel stride ld_res, same channels as y):
+    //   y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res])   -- the arithmetic of gbn_apply_kernel, bit for bit
+    // not with accumulate, the fused statistics or the sigmoid (the launchers return -22)
+    const float* scale = nullptr; const float* shift = nullptr; const float* res = nullptr; int ld_res = 0;
 };
+// the affine epilogue's own argument rules, checked by both launchers before their launch
+inline bool ptta_gx3_affine_ok(const GX3Args& a) {
+    if (!a.scale && !a.shift && !a.res) return true;
+    if (!a.scale || !a.shift || a.accumulate || a.stat_part || (a.act != GACT_NONE && a.act != GACT_RELU && a.act != GACT_LRELU)) return false;
+    return !a.res || a.ld_res >= a.Cy;
+}
 void ptta_gfrag_pack(const float* canon, long wld, long wts, int KK, int C0, int C1, int c0_0, int c0_1, int Co, bf16_t* hi, bf16_t* lo,
                      hipStream_t s, bf16_t* l2 = nullptr);
 long ptta_gfrag_elems(int KK, int C0, int C1, int Co);

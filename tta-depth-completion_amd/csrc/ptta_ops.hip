@@ -1,5 +1,5 @@
 // Entry points that take no handle: outlier removal, evaluation metrics, the modulated deformable convolution, and the
-// stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_gconv, ptta_op_gbn, ptta_op_conv32_chain).
+// stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_gconv, ptta_op_gconv_affine, ptta_op_gbn, ptta_op_conv32_chain).
 #include "msgchn_ctx.h"
 #include "gnet.h"
 
@@ -144,10 +144,18 @@ int ptta_op_gwgrad(const float* x, const float* gy, float* gw, float* gb, int b,
 // Stand-alone convolution of the generic engine on fp32 NHWC device views (tests): the weight is packed by the engine's own code
 // (gnet::pack_conv_weight / pack_vcol_weight) and launched ONCE the way GNet::run_conv_fwd / run_conv_bwd launch it -- the matrix-core
 // form (impl 0) or the direct fp32 form (impl 1, one launch per source).  include/ptta.h states the arguments.
-int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y, int co,
-                  int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl, int flags,
-                  int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, ptta_stream s_) {
+// affine: ptta_op_gconv_affine's epilogue (scale / shift / res / ld_res; the matrix-core forms only), refused before the first launch
+static int op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y, int co,
+                    int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl, int flags,
+                    int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, bool affine, const float* scale, const float* shift,
+                    const float* res, int ld_res, ptta_stream s_) {
     hipStream_t s = (hipStream_t)s_;
+    if (affine) {
+        const int cm = geom == PTTA_GCONV_S1 ? 7 : 15;          // channel counts the matrix-core forms take (ptta_launch_gconv_x3 / _strided)
+        if (!scale || !shift || (((size_t)scale | (size_t)shift) & 15) || (res != nullptr) != (ld_res != 0) || (res && ld_res < co) ||
+            impl != 0 || accumulate || stat_npass || six_b || (flags & PTTA_GCONV_DGRAD) || (act != GACT_NONE && act != GACT_RELU && act != GACT_LRELU) ||
+            c0 < 1 || c1 < 0 || (c0 & cm) || (c1 & cm)) return -22;
+    }
     const bool vert = flags & PTTA_GCONV_VERT, dgrad = flags & PTTA_GCONV_DGRAD;
     if (!x0 || !weight || !y || b < 1 || hin < 1 || win < 1 || hout < 1 || wout < 1 || c0 < 1 || c1 < 0 || co < 1 || ld0 < c0 || ldy < co ||
         (c1 > 0) != (x1 != nullptr) || (c1 > 0 && ld1 < c1) || (k != 1 && k != 3) || geom < PTTA_GCONV_S1 || geom > PTTA_GCONV_T2 ||
@@ -201,6 +209,7 @@ int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int
             if (six_b > 0) { a.wl2 = (const uint4*)cw.ff_l2; a.six_B = six_b; }
             a.x1_from_B = x1_from_b; a.x1_w2 = (flags & PTTA_GCONV_X1_W2) ? 1 : 0;
             if (stat) { a.stat_part = stat; a.stat_C = co; a.stat_npass = stat_npass; }
+            if (affine) { a.scale = scale; a.shift = shift; a.res = res; a.ld_res = ld_res; }
             if (run == PTTA_GCONV_S1) rc = ptta_launch_gconv_x3(a, k, s);
             else {
                 const int mode = run == PTTA_GCONV_T2 ? 2 : 1;
@@ -241,6 +250,20 @@ int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int
     }
     (void)hipFree(wbuf); (void)hipFree(fbuf); (void)hipFree(stat);
     return rc;
+}
+int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y, int co,
+                  int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl, int flags,
+                  int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, ptta_stream s_) {
+    return op_gconv(x0, c0, ld0, x1, c1, ld1, weight, bias, y, co, ldy, b, hin, win, hout, wout, k, geom, act, accumulate, impl, flags, six_b, x1_from_b,
+                    stat_npass, stat_host, form_host, false, nullptr, nullptr, nullptr, 0, s_);
+}
+// the same convolution with the eval-BatchNorm epilogue of the meta-only mode: y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res])
+int ptta_op_gconv_affine(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y, int co,
+                         int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl, int flags,
+                         int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, const float* scale, const float* shift,
+                         const float* res, int ld_res, ptta_stream s_) {
+    return op_gconv(x0, c0, ld0, x1, c1, ld1, weight, bias, y, co, ldy, b, hin, win, hout, wout, k, geom, act, accumulate, impl, flags, six_b, x1_from_b,
+                    stat_npass, stat_host, form_host, true, scale, shift, res, ld_res, s_);
 }
 
 // Stand-alone BatchNorm of the generic engine on fp32 NHWC device views (tests): the launchers of gbn.hip called as GNet::run_bn_fwd /

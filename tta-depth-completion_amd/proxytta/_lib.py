@@ -19,6 +19,7 @@ PTTA_BACKBONE_COSTDCNET = 2
 PTTA_NLSPN_LEGACY_OFFSET = 0x100
 PTTA_NLSPN_SYNCBN_ADAPT = 0x200
 PTTA_SYNCBN_ADAPT = 0x200
+PTTA_ADAPT_META_ONLY = 0x400
 PTTA_META_1LAYER = 0
 PTTA_META_2LAYERS = 1
 PTTA_DTYPE_F32 = 0
@@ -115,6 +116,8 @@ SIGNATURES = [
     ('ptta_op_conv32_chain', c_int, [_P] * 6 + [c_int] * 7 + [POINTER(c_float), _P]),
     ('ptta_op_gwgrad', c_int, [_P, _P, _P, _P] + [c_int] * 7 + [POINTER(c_float), _P]),
     ('ptta_op_gconv', c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, _P, _P] + [c_int] * 16 + [POINTER(ctypes.c_double), POINTER(c_int), _P]),
+    ('ptta_op_gconv_affine', c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, _P, _P] + [c_int] * 16 + [POINTER(ctypes.c_double), POINTER(c_int),
+                                     _P, _P, _P, c_int, _P]),
     ('ptta_op_gbn', c_int, [POINTER(GbnArgs), _P]),
     ('ptta_version', c_int, []),
 ]

@@ -52,7 +52,7 @@ class Engine:
     def __init__(self, n, height, width, dtype='fp32', lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, w_sparse_depth=1.0, w_smoothness=1.0, w_cos=1.0,
                  max_input_depth=None, meta='1layer', backbone='msg_chn', legacy_offset=False, max_predict_depth=None,
-                 syncbn_adapted=False, keep=(), options=None):
+                 syncbn_adapted=False, keep=(), options=None, adapt_mode='meta_bn'):
         if not torch.cuda.is_available():
             raise RuntimeError('proxytta needs a HIP device (torch.cuda.is_available() is False); '
                                'there is no CPU fallback')
@@ -61,6 +61,10 @@ class Engine:
         self.dtype = dtype
         self.meta = meta
         self.backbone = backbone
+        if adapt_mode not in ('meta_bn', 'meta', 'meta_fix'):
+            raise ValueError("adapt_mode must be 'meta_bn', 'meta' or 'meta_fix' (src/nlspn_model_adapt.py:302-337)")
+        # 'meta' / 'meta_fix' (NLSPN): the meta conv alone adapts, BatchNorm2d evaluates from its loaded running statistics (include/ptta.h PTTA_ADAPT_META_ONLY)
+        self.adapt_mode = adapt_mode
         self.emb_dim = 1024 if backbone == 'nlspn' else 512
         if backbone == 'costdcnet' and not max_predict_depth:
             raise ValueError('CostDCNet needs max_predict_depth (the far plane of its cost volume, ExternalModel_Adapt(max_predict_depth))')
@@ -79,13 +83,15 @@ class Engine:
                                   {'nlspn': _lib.PTTA_BACKBONE_NLSPN, 'costdcnet': _lib.PTTA_BACKBONE_COSTDCNET}.get(backbone, _lib.PTTA_BACKBONE_MSG_CHN),
                                   (_lib.PTTA_META_2LAYERS if meta == '2layers' else _lib.PTTA_META_1LAYER) |
                                   (_lib.PTTA_NLSPN_LEGACY_OFFSET if (legacy_offset and backbone == 'nlspn') else 0) |
-                                  (_lib.PTTA_SYNCBN_ADAPT if (syncbn_adapted and backbone in ('nlspn', 'costdcnet')) else 0),
+                                  (_lib.PTTA_SYNCBN_ADAPT if (syncbn_adapted and backbone in ('nlspn', 'costdcnet')) else 0) |
+                                  (_lib.PTTA_ADAPT_META_ONLY if adapt_mode != 'meta_bn' else 0),
                                   self.n, self.h, self.w, code, byref(self.hp))
         if rc != 0:
             why = {-19: 'no HIP device', -12: 'out of device memory', -22: 'invalid size / argument',
                    -38: 'configuration not on the accelerated path (every backbone runs the 1layer and the 2layers meta layer; '
                         'CostDCNet in fp32 only; the 2layers block not with the SyncBN-adapted set of NLSPN / CostDCNet)'}.get(rc, 'see include/ptta.h')
-            raise RuntimeError('ptta_create failed (%d): %s' % (rc, why))
+            said = self.lib.ptta_last_error(None).decode()      # the reason of a refused configuration, where the library states one
+            raise RuntimeError('ptta_create failed (%d): %s' % (rc, said if (rc == -38 and said != 'null handle') else why))
         for k, v in (options or {}).items():       # include/ptta.h ptta_set_option
             self.set_option(k, v)
         self.rows = int(self.lib.ptta_embedding_rows(self.handle))
@@ -543,6 +549,33 @@ def op_gconv(x0, weight, y, x1=None, bias=None, k=3, geom='s1', act='none', accu
         raise RuntimeError('ptta_op_gconv failed (%d)' % rc)
     st = torch.tensor(list(stats), dtype=torch.float64).view(stat_npass, 2, co) if stat_npass else None
     return GCONV_FORMS[form.value], st
+
+
+def op_gconv_affine(x0, weight, y, scale, shift, x1=None, bias=None, res=None, ld_res=None, k=3, geom='s1', act='none', impl='mfma',
+                    accumulate=False):
+    """Test hook: op_gconv with the eval-BatchNorm epilogue of NLSPN's meta-only mode (include/ptta.h ptta_op_gconv_affine):
+    y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res]).  scale / shift [co] device tensors; res [b, hout, wout, co], possibly a channel
+    slice of a wider tensor; ld_res overrides the residual's pixel stride (the argument checks).  Returns the strided launch form."""
+    lib = _lib.load()
+
+    def view(t):
+        b, h, w, c = t.shape
+        ld = t.stride(2)
+        assert t.dtype == torch.float32 and t.stride(3) == 1 and t.stride(1) == w * ld and t.stride(0) == h * w * ld and ld >= c
+        return c_void_p(t.data_ptr()), c, ld
+    b, hin, win, _ = x0.shape
+    hout, wout = y.shape[1], y.shape[2]
+    p0, c0, ld0 = view(x0)
+    p1, c1, ld1 = view(x1) if x1 is not None else (None, 0, 0)
+    py, co, ldy = view(y)
+    pr, _, ldr = view(res) if res is not None else (None, 0, 0)
+    form = c_int(-1)
+    rc = lib.ptta_op_gconv_affine(p0, c0, ld0, p1, c1, ld1, ptr(weight.contiguous()), ptr(bias), py, co, ldy, b, hin, win, hout, wout, k,
+                                  GCONV_GEOMS[geom], GCONV_ACTS[act], int(bool(accumulate)), GCONV_IMPLS[impl], 0, 0, 1 << 30, 0, None,
+                                  byref(form), ptr(scale), ptr(shift), pr, ldr if ld_res is None else int(ld_res), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_gconv_affine failed (%d)' % rc)
+    return GCONV_FORMS[form.value]
 
 
 GBN_MODES = {'train': 0, 'eval': 1, 'backward': 2}

@@ -6,6 +6,8 @@ prepare_mode 'meta_selfsup_seq_1layer_ema', adapt_mode 'meta_bn', loss_type 'ada
 the reference's own call sequence ``forward`` / ``compute_loss`` / ``loss.backward()`` / ``optimizer.step()``
 (src/tta_main.py:610-633, autograd Functions over ptta_forward_train / ptta_loss_* / ptta_backward), the fused
 ``step()`` (the same in one library call, Adam on device for the 88 adapted tensors) and the eval ``forward()`` (:729-736).
+adapt_mode 'meta' / 'meta_fix' (src/nlspn_model_adapt.py:302-320) run on the same path with two adapted tensors: the meta conv alone
+adapts, every BatchNorm2d keeps its loaded running statistics and evaluates from them in the scored eval forward (adapt_parameters below).
 Any frame size from 16 x 16 up: encoder maps of odd size make the decoder maps one row / column larger and they are cropped
 before each concatenation as in nlspnmodel_adapt.py:474-490 (NYUv2's 228 x 304 is such a size).
 The eval path's biharmonic hole filling (src/nlspn_model_adapt.py:124-127, skimage on the CPU) is not applied: exact
@@ -20,6 +22,12 @@ from .costdcnet import _unique
 from .model import MsgChnModel_Adapt, _ForwardFn, _init_tensor, _Tree
 
 _BUFFERS = ('running_mean', 'running_var', 'num_batches_tracked')
+
+
+def nlspn_meta_names(keys):
+    """adapt_parameters('meta') and ('meta_fix') (src/nlspn_model_adapt.py:302-320): the parameters whose name contains 'meta', in
+    named_parameters order -- conv1_rgb_meta.weight, conv1_rgb_meta.bias under the 1layer meta conv.  No BatchNorm parameter is listed."""
+    return [k for k in keys if 'meta' in k and not k.endswith(_BUFFERS)]
 
 
 def nlspn_adapted_names(keys, syncbn=False):
@@ -50,6 +58,7 @@ class NlspnModel_Adapt(MsgChnModel_Adapt):
         self.dtype = 'fp32'
         self.training = True
         self.prepare_mode = None
+        self.adapt_mode = 'meta_bn'
         self.model = _Tree()
         for k, s in synth.nlspn_keys():
             if k.startswith(('proj', 'pred', 'conv1_rgb_meta')):
@@ -93,7 +102,8 @@ class NlspnModel_Adapt(MsgChnModel_Adapt):
 
     def _set_adapted(self):
         # adapted_listed: the reference's parameter list (2layers names the block's BatchNorm2d twice); adapted: the tensors behind it
-        self.adapted_listed = nlspn_adapted_names([k for k, _ in synth.nlspn_keys(self.prepare_mode)], self.sync_bn)
+        keys = [k for k, _ in synth.nlspn_keys(self.prepare_mode)]
+        self.adapted_listed = nlspn_adapted_names(keys, self.sync_bn) if self.adapt_mode == 'meta_bn' else nlspn_meta_names(keys)
         self.adapted = _unique(self.adapted_listed)
         self._clear_engines()
 
@@ -105,8 +115,23 @@ class NlspnModel_Adapt(MsgChnModel_Adapt):
             self._set_adapted()
 
     def adapt_parameters(self, mode=None):
-        if mode != 'meta_bn':
-            raise NotImplementedError("adapt_mode %r: only 'meta_bn' (the NLSPN scripts' mode) is on the accelerated path" % mode)
+        """src/nlspn_model_adapt.py:287-340.  'meta_bn' (the NLSPN scripts' mode): the meta layer + gamma / beta of every BatchNorm2d, which
+        lose their running statistics (batch statistics in train and eval mode).  'meta' (the method itself) and 'meta_fix': the meta conv's
+        weight and bias only; every BatchNorm2d keeps its loaded buffers with track_running_stats = False -- batch statistics in train-mode
+        passes, no buffer written, and the LOADED running statistics and gamma / beta in the scored eval forward.  The two differ in the
+        reference only by the requires_grad flags of the frozen BatchNorm parameters, which no optimiser sees: in one process they are
+        numerically identical, and both select the same engine mode here (include/ptta.h PTTA_ADAPT_META_ONLY).  The mode holds for the
+        engines created afterwards; switching it releases the existing ones, as _prepare_head does."""
+        if mode not in ('meta_bn', 'meta', 'meta_fix'):
+            raise NotImplementedError("adapt_mode %r: 'meta_bn' (the NLSPN scripts' mode), 'meta' and 'meta_fix' are on the accelerated path" % mode)
+        if self.prepare_mode is None:
+            raise RuntimeError('_prepare_head(mode) must be called before adapt_parameters (tta_main.py:322, :339)')
+        if mode != 'meta_bn' and (self.meta == '2layers' or self.sync_bn):
+            raise NotImplementedError("adapt_mode %r runs with the 1layer meta conv on one rank (the 2layers block and the SyncBatchNorm "
+                                      "form of this mode are not built)" % mode)
+        if mode != self.adapt_mode:
+            self.adapt_mode = mode
+            self._set_adapted()                    # new list; releases the engines of the other mode
         params = dict(self.model.named_parameters())
         # 2layers: four tensors listed twice -- torch.optim.Adam steps them twice per step(), as the reference's (torch 1.10.1; with torch >= 2.0
         # on the GPU build the optimizer with foreach=False for the same), and the fused step() does the same on device
@@ -120,7 +145,7 @@ class NlspnModel_Adapt(MsgChnModel_Adapt):
             if self.prepare_mode is None:
                 raise RuntimeError('_prepare_head(mode) must be called before forward (tta_main.py:322)')
             eng = Engine(n, h, w, backbone='nlspn', legacy_offset=self.legacy, max_input_depth=self.max_input_depth,
-                         syncbn_adapted=self.sync_bn, meta=self.meta, **self.hparams)
+                         syncbn_adapted=self.sync_bn, meta=self.meta, adapt_mode=self.adapt_mode, **self.hparams)
             assert all(self.adapted_listed.count(k) == max(eng.adapted_repeat[k], 1) for k in eng.adapted), 'listing counts drifted'
             assert eng.adapted == self.adapted, 'adapted parameter list drifted from the library'
             eng.load_state_dict(self.model.state_dict())     # the heads' BatchNorm1d buffers are bound and updated in place
