@@ -417,7 +417,7 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  * handle's streams and drops its captured graphs; the next step re-captures.  Every non-default value is a correct, slower form of
  * the same step, kept as the check of the default (tests/test_gpu_options.py) or taken by the library itself where the default
  * form does not apply (small maps, N > 16, SyncBatchNorm exchange).  Unknown key / value out of range: -22; a key the handle does
- * not have: -38 (the generic engine has "graph" and, on PTTA_ADAPT_META_ONLY handles, "eval_bn_fused"; PTTA_DTYPE_MIXED handles keep every key but graph / aux_stream / thru / adam_in_wgrad at 1).
+ * not have: -38 (the generic engine has "graph", "head_bn_fused" and, on PTTA_ADAPT_META_ONLY handles, "eval_bn_fused"; PTTA_DTYPE_MIXED handles keep every key but graph / aux_stream / thru / adam_in_wgrad at 1).
  *   key             default  meaning of 0
  *   "graph"         0        (1:) ptta_step / ptta_step_pipelined / ptta_forward_eval replay captured hipGraphs from their second call on.  Default
  *                            since round 5: direct launches on the caller's stream and the handle's own streams -- measured FASTER than replay
@@ -444,11 +444,26 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  *   "eval_bn_fused" 1        (PTTA_ADAPT_META_ONLY handles only, -38 elsewhere) 0: every BatchNorm2d of the eval forward is its own apply launch
  *                            from the same affine table (1: in the epilogue of the convolution in front of it).  Bit-identical
  *                            (tests/test_gpu_nlspn_meta.py): both forms compute fmaf(conv + bias, scale, shift)
+ *   "head_bn_fused" 1        (NLSPN and CostDCNet handles; -38 on MSG_CHN, which has no BatchNorm2d) 0: in the stage-2 head trainer's two
+ *                            no-gradient backbone passes (ptta_head_forward / ptta_head_step, both forms of ptta_head_set_form) every frozen
+ *                            BatchNorm2d is an affine-table launch and an apply launch of its own (1: all tables of the prefix are built by ONE
+ *                            launch per head forward, from the gamma / beta bound at that call, and each BatchNorm2d runs in the epilogue of the
+ *                            convolution in front of it: NLSPN's conv1 .. conv6, CostDCNet's Encoder2D, the 2layers block of either; bf16x6
+ *                            images keep bf16x6).  Bit-identical (tests/test_gpu_head_bn_fused.py).  BatchNorm3d, the sparse encoder's
+ *                            BatchNorm, the heads' BatchNorm1d and PTTA_DTYPE_MIXED handles keep their separate launches either way.  With 1 a
+ *                            head forward does not write the raw convolution outputs of the fused pairs (see ptta_debug_tensor).
+ *                            Measured on MI355X, head step, 1 against 0 alternating in one process (profiles/head_bn_fused.txt,
+ *                            tools/bench_head_generic.py): NLSPN 352x1216 9.49 against 10.63 ms (N 1), 17.47 against 19.66 (N 2); CostDCNet 480x640
+ *                            4.94 against 5.42 (N 1), 8.31 against 9.21 (N 2); 0 equals the step before the option within the run-to-run spread.
+ *                            Faster on both backbones, hence 1 on both
  * Read-only keys (ptta_get_option; -22 from ptta_set_option):
  *   "pipelined_active"  1 when ptta_step_pipelined runs as itself on this handle as configured now; 0 when it degrades to ptta_step call by call
  *                       (generic-engine backbones, the dual-corner padded path, a statistics exchange or a gradient communicator bound,
  *                       validation arithmetic, the profiling leg) -- same results, the call-by-call price
  *   "thru_active"       1 when the step takes the two-stream `thru` schedule
+ *   "head_bn_fused_count"  how many BatchNorm2d of this handle's stage-2 prefix ride in a convolution epilogue as configured now: 36 (NLSPN),
+ *                       38 (NLSPN 2layers), 15 (CostDCNet), 17 (CostDCNet 2layers); 0 with "head_bn_fused" 0, on a PTTA_DTYPE_MIXED handle and with
+ *                       PTTA_CONV_IMPL=naive (no matrix-core convolution to ride in); -38 on MSG_CHN
  * bit-identical to the default: aux_stream, thru, adam_in_wgrad, fuse_first, fuse_head_bwd, mask_bits, graph; within bf16x3's own error (documented
  * in the tests): fuse_heads, heads_v2, cos_in_gemm.
  * Environment, read once per ptta_create (csrc/ptta_kernels.h ptta_create_env) because it decides allocation and arithmetic:
@@ -469,7 +484,10 @@ int ptta_profile(ptta_handle h, int enable);
 int ptta_profile_read(ptta_handle h, int klass, double* ms_total_host, double* alg_bytes_host, double* macs_host,
                       int64_t* launches_host, ptta_stream s);
 
-/* Test / debug hooks (not on the hot path). */
+/* Test / debug hooks (not on the hot path).  ptta_debug_tensor reads a named activation of the last forward.  With "head_bn_fused" 1 a head
+ * forward does NOT write the raw convolution output in front of a fused BatchNorm2d (NLSPN "conv2.0.r1", CostDCNet "enc2d.layer1.0.r1", ...;
+ * likewise "eval_bn_fused" and the eval forward of a PTTA_ADAPT_META_ONLY handle): such a name then returns what an earlier TTA forward left
+ * there.  Set the option to 0 to read them. */
 int ptta_debug_tensor(ptta_handle h, const char* name, float* dst, int64_t capacity, int64_t* numel_host, ptta_stream s);
 int ptta_op_conv32(const float* in_nhwc, const float* weight, const float* bias, float* out_nhwc,
                    int b, int hin, int win, int mode, int relu_in, int in_major, int flip, int dtype, int naive,
@@ -506,17 +524,26 @@ int ptta_op_gwgrad(const float* x_nhwc, const float* gy_nhwc, float* gw, float* 
 #define PTTA_GCONV_VERT 1
 #define PTTA_GCONV_X1_W2 2
 #define PTTA_GCONV_DGRAD 4
+#define PTTA_GCONV_AFF_ACT_FIRST 8      /* ptta_op_gconv_affine only (-22 from ptta_op_gconv) */
+#define PTTA_GCONV_AFF_RES_PLAIN 16     /* ptta_op_gconv_affine only */
 int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y,
                   int co, int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl,
                   int flags, int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, ptta_stream s);
-/* The same hook with the epilogue of the PTTA_ADAPT_META_ONLY eval forward: a BatchNorm2d with constant statistics behind the convolution,
- *   y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res])
+/* The same hook with the epilogue of the PTTA_ADAPT_META_ONLY eval forward and of the stage-2 head trainer (option "head_bn_fused"): a
+ * BatchNorm2d with constant statistics behind the convolution,
+ *   y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res])                    no flag; with res: act 1, the BasicBlock's ReLU behind the sum
+ *   y = relu(relu(fmaf(conv + bias, scale[c], shift[c])) + res)               PTTA_GCONV_AFF_ACT_FIRST: CostDCNet's ResBlock; res and act 1 required
+ *   y = fmaf(conv + bias, scale[c], shift[c]) + res                           PTTA_GCONV_AFF_RES_PLAIN: the 2layers block's last BatchNorm2d; res and act 0
  * scale / shift [co]: the {scale, shift} rows of an eval affine table (what PTTA_GBN_EVAL leaves in st + 2 co and st + 3 co), 16-byte
- * aligned; res: the BasicBlock residual, a view [b][hout][wout] of co channels with pixel stride ld_res >= co, added before the activation,
- * or NULL with ld_res 0.  Bit-identical to ptta_op_gconv with act 0 followed by ptta_op_gbn in mode PTTA_GBN_EVAL with the same activation
- * (res_relu 1 and act 1 with a residual).  Matrix-core forms only, every geometry: impl 0, c0 and c1 multiples of 8 (PTTA_GCONV_S1) or 16,
- * act 0 / 1 / 2, no accumulate, no statistics, no bf16x6, no PTTA_GCONV_DGRAD.  -22 BEFORE any launch for anything else, for a NULL or
- * misaligned scale / shift, and for res without ld_res (or the reverse, or ld_res < co). */
+ * aligned; res: the residual, a view [b][hout][wout] of co channels with pixel stride ld_res >= co, or NULL with ld_res 0.
+ * Bit-identical to ptta_op_gconv with act 0 and the same six_b followed by ptta_op_gbn in mode PTTA_GBN_EVAL with the same act and, with a
+ * residual, act_first 0 / res_relu 1 (no flag), act_first 1 / res_relu 1 (ACT_FIRST), act_first 0 / res_relu 0 (RES_PLAIN)
+ * (tests/test_gpu_gconv_affine.py, tests/test_gpu_gconv_affine_forms.py).  Matrix-core forms only: impl 0, c0 and c1 multiples of 8
+ * (PTTA_GCONV_S1) or 16, act 0 / 1 / 2, no accumulate, no statistics, no PTTA_GCONV_DGRAD.  six_b as in ptta_op_gconv: the images below it
+ * bf16x6, with every form above, on PTTA_GCONV_S1 and every launch form of PTTA_GCONV_S2.  PTTA_GCONV_T2 has the first form in bf16x3 only
+ * (no stage-2 prefix holds a transposed layer).  -22 BEFORE any launch for anything else: ACT_FIRST without res or with an activation other
+ * than ReLU, RES_PLAIN without res or with an activation, both flags, six_b > b, a NULL or misaligned scale / shift, res without ld_res (or
+ * the reverse, or ld_res < co). */
 int ptta_op_gconv_affine(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y,
                          int co, int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl,
                          int flags, int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, const float* scale,

@@ -141,6 +141,7 @@ struct costdc_engine : GNet {
             Op& c2 = conv(MP + ".1", ma, -1, mr, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH); c2.ad_w = ad_mw; c2.ad_b = ad_mb;
             bn(MP + ".2", mr, t_feat2d, f16, GACT_NONE, W_BOTH).res_relu = false;        // conv1_meta(x) + x: no ReLU after the sum
         }
+        const int enc2d_ops_end = (int)ops.size();             // ops [0, enc2d_ops_end) = Encoder2D and the meta conv / block
         if (sync_adapt) {
             // convert_sync_batchnorm makes one new module per visited attribute: ResBlock.norm3 and its alias downsample[1] become two
             // SyncBatchNorm modules sharing one Parameter, which adapt_parameters then lists twice -> two Adam updates per step
@@ -244,6 +245,7 @@ struct costdc_engine : GNet {
         t_emb = mlp("pred", pz, false); tid["emb"] = t_emb;
         t_ref = mlp("proj_t", t_rows, true); tid["ref"] = t_ref;
         plan_backward({t_ref});
+        plan_head_affine(enc2d_ops_end);                       // stage-2 head trainer: the BatchNorm2d of that prefix (head_features)
         // ---- remaining workspace ----
         const long P = (long)H * W;
         if (dual) { img_pad = falloc((size_t)N * 3 * P); sp_pad = falloc((size_t)N * P); }

@@ -460,6 +460,23 @@ __global__ void gbn_eval_affine_kernel(const float* __restrict__ gamma, const fl
     const float iv = 1.f / sqrtf(rv[c] + eps), sc = gamma[c] * iv;
     st[c] = rm[c]; st[C + c] = iv; st[2 * C + c] = sc; st[3 * C + c] = beta[c] - rm[c] * sc;
 }
+// the same tables for a list of BatchNorms in ONE launch (the stage-2 head trainer's prefix, GNet::prepare_head_affines): block row = entry,
+// the expressions of gbn_eval_affine_kernel word for word, so that both build the same bits
+__global__ void gbn_eval_affine_multi_kernel(const GbnEvalEntry* __restrict__ tab, float eps) {
+    const GbnEvalEntry e = tab[blockIdx.y];
+    const int c = blockIdx.x * blockDim.x + threadIdx.x, C = (int)e.C;
+    if (c >= C) return;
+    const float* __restrict__ gamma = e.gamma; const float* __restrict__ beta = e.beta;
+    const float* __restrict__ rm = e.rm; const float* __restrict__ rv = e.rv; float* __restrict__ st = e.st;
+    const float iv = 1.f / sqrtf(rv[c] + eps), sc = gamma[c] * iv;
+    st[c] = rm[c]; st[C + c] = iv; st[2 * C + c] = sc; st[3 * C + c] = beta[c] - rm[c] * sc;
+}
+int ptta_launch_gbn_eval_affine_multi(const GbnEvalEntry* tab_dev, int n, int max_C, float eps, hipStream_t s) {
+    if (n < 1 || n > 65535 || max_C < 1) return -22;
+    hipLaunchKernelGGL(gbn_eval_affine_multi_kernel, dim3((max_C + 255) / 256, n), dim3(256), 0, s, tab_dev, eps);
+    PTTA_CHECK_LAUNCH();
+    return 0;
+}
 int ptta_launch_gbn_eval_affine(const float* gamma, const float* beta, const float* rm, const float* rv, float eps, int C, float* st, hipStream_t s) {
     hipLaunchKernelGGL(gbn_eval_affine_kernel, dim3((C + 255) / 256), dim3(256), 0, s, gamma, beta, rm, rv, eps, C, st);
     PTTA_CHECK_LAUNCH();

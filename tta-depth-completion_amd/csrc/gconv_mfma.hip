@@ -84,7 +84,9 @@ __global__ void gfrag_pack_kernel(const float* __restrict__ canon, long wld, lon
 #define STAMP(v) do { if constexpr (TIMING) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); v = t_; } } while (0)
 // SIX: three operand planes (GX3Args::six_B): 112 B of LDS per pixel, three weight planes, two blocks per CU; blocks of images
 // >= six_B (the proxy frames) skip the three extra products
-template <int KS, bool VERT, bool TIMING = false, bool SIX = false>
+// ACTF: the affine epilogue's act_first form, relu(relu(fmaf(..)) + res) (GX3Args::aff_act_first): the inner ReLU in the register layout,
+// an instantiation of its own so that the others keep their code
+template <int KS, bool VERT, bool TIMING = false, bool SIX = false, bool ACTF = false>
 __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p) {
     unsigned long long T0 = 0, ta = 0, tb = 0, tc = 0, td = 0, te = 0, tf = 0, tg = 0;
     unsigned long long dA = 0, dW = 0, dS = 0, dL = 0, dB = 0, dM = 0;
@@ -303,6 +305,7 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
                 const int px = acc_row(r, h);
                 float v = sig ? acc[rr][r] : acc[rr][r] + bias_w;
                 if (p.scale) v = fmaf(v, asc, ash);
+                if constexpr (ACTF) v = v > 0.f ? v : 0.f;
                 if (!p.accumulate) {
                     v = (sig || p.res) ? v : activate_cheap(v);
                     if (yok && cok && x0 + px < W) { s1 += v; s2 += v * v; }
@@ -353,6 +356,7 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
             float* dst = yrow + (size_t)x * p.ldy;
             float v = acc[rr][r] + bias;
             if (p.scale) v = fmaf(v, asc, ash);
+            if constexpr (ACTF) v = v > 0.f ? v : 0.f;
             if (p.accumulate) v += *dst;
             if (p.res) v += p.res[(((size_t)b * H + y) * W + x) * p.ld_res + co];
             v = activate(v);
@@ -397,8 +401,11 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
 // bf16 in registers) feeds two weight fragments
 // SIX: bf16x6 for the images below p.six_B (GX3Args), the third operand planes split in registers / streamed like the other two
 // AFF: the per-channel affine + residual epilogue (GX3Args::scale).  An instantiation of its own: written as a run-time switch it cost the
-// K-split stride-2 forms two registers and with them their third wave per SIMD (136 + 32 -> 138 + 32, compiler's resource usage)
-template <int MODE, int KS, int KSPLIT, int NCO, bool SIX = false, bool AFF = false>
+// K-split stride-2 forms two registers and with them their third wave per SIMD (136 + 32 -> 138 + 32, compiler's resource usage).
+// AFF 2: the same with the act_first residual form, relu(relu(fmaf(..)) + res) (GX3Args::aff_act_first) -- again its own instantiation.
+// No engine prefix has an act_first BatchNorm behind a strided convolution (CostDCNet's follows the stride-1 conv2): the twelve stride-2 AFF 2
+// kernels are reached through ptta_op_gconv_affine only, 12 of this file's 72 kernels in compile time and code size
+template <int MODE, int KS, int KSPLIT, int NCO, bool SIX = false, int AFF = 0>
 __global__ __launch_bounds__(256) void gconv_x3_direct_kernel(GX3Args p, int Hin, int Win) {
     constexpr int PAD = KS / 2, KK = KS * KS;
     // stride 2: two output rows per wave, tap-outer / row-inner, so the A loads of both rows are in flight before the
@@ -560,6 +567,10 @@ __global__ __launch_bounds__(256) void gconv_x3_direct_kernel(GX3Args p, int Hin
                 const float asc = co < p.Cy ? p.scale[co] : 1.f, ash = co < p.Cy ? p.shift[co] : 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) tt[r] = fmaf(tt[r], asc, ash);
+                if constexpr (AFF == 2) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) tt[r] = tt[r] > 0.f ? tt[r] : 0.f;
+                }
             }
             quad_transpose(tt, lane);
             float* yrow = p.y + ((size_t)b * Hout + y) * Wout * p.ldy + c4;
@@ -603,6 +614,7 @@ __global__ __launch_bounds__(256) void gconv_x3_direct_kernel(GX3Args p, int Hin
             float* dst = yrow + (size_t)x * p.ldy;
             float v = acc[t][rr][r] + bias;
             if constexpr (AFF) v = fmaf(v, p.scale[co], p.shift[co]);
+            if constexpr (AFF == 2) v = v > 0.f ? v : 0.f;
             if (!AFF && p.accumulate) v += *dst;
             if (ares) v += ares[(((size_t)b * Hout + y) * Wout + x) * p.ld_res + co];
             *dst = activate(v);
@@ -941,6 +953,16 @@ int ptta_launch_gconv_x3(const GX3Args& a, int ks, hipStream_t s) {
     const long tiles = (long)a.B * ((a.W + 31) / 32) * ((a.H + GX_TH - 1) / GX_TH);
     const long blocks = tiles * a.nnf;
     if (blocks < 1 || blocks > 0x7fffffffL) return -22;
+    if (a.aff_act_first) {                 // relu(relu(affine) + res): its own instantiations (no vertical form: ptta_gx3_affine_ok)
+        if (a.six_B > 0 && !a.wl2) return -22;
+        if (ks == 3 && a.six_B > 0) hipLaunchKernelGGL((gconv_x3_s1_kernel<3, false, false, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else if (ks == 3) hipLaunchKernelGGL((gconv_x3_s1_kernel<3, false, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else if (ks == 1 && a.six_B > 0) hipLaunchKernelGGL((gconv_x3_s1_kernel<1, false, false, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else if (ks == 1) hipLaunchKernelGGL((gconv_x3_s1_kernel<1, false, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else return -22;
+        PTTA_CHECK_LAUNCH();
+        return 0;
+    }
     if (a.six_B > 0) {
         if (!a.wl2) return -22;
         if (ks == 3 && a.vert) hipLaunchKernelGGL((gconv_x3_s1_kernel<3, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
@@ -985,13 +1007,18 @@ int ptta_launch_gconv_x3_strided(const GX3Args& a, int ks, int mode, int hin, in
     const long blocks = (split ? nitems : (nitems + 3) / 4) * ngrp;
     if (blocks < 1 || blocks > 0x7fffffffL) return -22;
     if (a.six_B > 0 && !a.wl2) return -22;
-    if (a.scale) {                         // the affine epilogue's instantiations (bf16x3 only: the eval forward of NLSPN's meta-only mode)
-        if (a.six_B > 0) return -22;
-#define LA_(M, K) do { if (nco == 2) hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 1, 2, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); \
-                      else if (split) hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 4, 1, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); \
-                      else hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 1, 1, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); } while (0)
-        if (mode == 1) { if (ks == 3) LA_(1, 3); else LA_(1, 1); }
-        else { if (ks == 3) LA_(2, 3); else LA_(2, 1); }
+    if (a.scale) {                         // the affine epilogue's instantiations
+        // bf16x3 with the plain epilogue in both geometries (the eval forward of NLSPN's meta-only mode); bf16x6 images and the act_first
+        // form on the stride-2 convolution only (the stage-2 prefixes hold no transposed layer)
+        if (mode == 2 && (a.six_B > 0 || a.aff_act_first)) return -22;
+#define LA_(M, K, S, A) do { if (nco == 2) hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 1, 2, S, A>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); \
+                      else if (split) hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 4, 1, S, A>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); \
+                      else hipLaunchKernelGGL((gconv_x3_direct_kernel<M, K, 1, 1, S, A>), dim3((unsigned)blocks), dim3(256), 0, s, a, hin, win); } while (0)
+#define LS_(K) do { if (a.six_B > 0) { if (a.aff_act_first) LA_(1, K, true, 2); else LA_(1, K, true, 1); } \
+                    else { if (a.aff_act_first) LA_(1, K, false, 2); else LA_(1, K, false, 1); } } while (0)
+        if (mode == 1) { if (ks == 3) LS_(3); else LS_(1); }
+        else { if (ks == 3) LA_(2, 3, false, 1); else LA_(2, 1, false, 1); }
+#undef LS_
 #undef LA_
         PTTA_CHECK_LAUNCH();
         return 0;

@@ -241,7 +241,8 @@ int GNet::head_forward(const float* image, const float* sparse, int reverse, flo
     }
     drop_graphs();
     bn_prepare = sync_form ? 2 : 1;
-    const int rcf = head_features(image, sparse, s);
+    int rcf = prepare_head_affines(s);          // the fused BatchNorm2d's tables, from the gamma / beta bound at this call
+    if (!rcf) rcf = head_features(image, sparse, s);
     bn_prepare = 0;
     fwd_valid = false;                   // not a forward ptta_backward may follow
     if (rcf) return rcf;

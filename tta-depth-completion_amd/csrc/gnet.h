@@ -97,6 +97,10 @@ struct Op {
     // place in the op list (the BasicBlock residual exists by then); that CONV op (aff_fused) is skipped at its own place
     int aff_from = -1;
     bool aff_fused = false;
+    // the same pairing for the stage-2 head trainer's no-gradient passes (GNet::plan_head_affine, option "head_bn_fused"): this BatchNorm2d,
+    // evaluated from its loaded running statistics under bn_prepare, rides in the CONV op hb_from; that op (hb_fused) is skipped at its place
+    int hb_from = -1;
+    bool hb_fused = false;
     bool no_dx = false;               // (CONV) no data gradient into the source although it has a gradient buffer (head trainer: detached input)
     float* st_eval = nullptr;         // tracked: eval-mode affine [mean, inv, scale, shift][C] of the running statistics
     mutable bool st_eval_valid = false;   // written by the last training forward's finalize (or an eval forward); cleared by every load()
@@ -204,8 +208,25 @@ struct GNet {
     // per-channel affine (Op::st_eval, built once per load by prepare_eval_affines) that runs in the producing convolution's epilogue
     // (eval_bn_fused, option "eval_bn_fused") or as a separate gbn_apply; no statistics pass either way
     int meta_only = 0, eval_bn_fused = 1;
-    void plan_eval_affine();
+    void plan_eval_affine() { plan_affine((int)ops.size(), false); }
     int prepare_eval_affines(hipStream_t s);
+    void plan_affine(int end, bool stage2);
+    // stage-2 head trainer (ghead.hip): the BatchNorm2d of the backbone prefix that head_features runs -- ops [0, head_bn_end) -- are in eval
+    // mode over both no-gradient passes, so with head_bn_fused (option "head_bn_fused", default 1) each rides in its convolution's epilogue
+    // (Op::hb_from).  gamma / beta of these ops are adapted tensors that a TTA step moves: every head_forward rebuilds all tables of the prefix
+    // from the tensors bound at that moment, in one launch (prepare_head_affines), and nothing is kept across calls.  Mixed-precision handles
+    // keep the separate applies (the proxy half's single-product arithmetic was never measured with the epilogue).
+    int head_bn_fused = 1, head_bn_end = 0;
+    void plan_head_affine(int end) { head_bn_end = end; plan_affine(end, true); }
+    bool head_fused_on() const { return head_bn_fused && !mixed; }
+    int head_bn_fused_count() const {
+        int n = 0;
+        if (head_fused_on()) for (int i = 0; i < head_bn_end && i < (int)ops.size(); ++i) n += ops[i].kind == gnet::K_BN && ops[i].hb_from >= 0;
+        return n;
+    }
+    GbnEvalEntry* hb_tab = nullptr; int hb_tab_cap = 0;
+    std::vector<GbnEvalEntry> hb_host, hb_sent;
+    int prepare_head_affines(hipStream_t s);
     PttaStatSync stat_sync;               // SyncBatchNorm exchange (ptta_set_stat_sync); world == 1: off
     void* grad_comm = nullptr;            // RCCL communicator of the gradient all-reduce inside step() (ptta_set_grad_sync_rccl)
 
@@ -463,6 +484,7 @@ struct GNet {
             if (limit >= 0 && idx++ >= limit) break;
             if (o.train_only && !train) continue;
             if (o.aff_fused && !train && meta_only && eval_bn_fused) continue;       // runs at its BatchNorm's place (run_bn_fwd)
+            if (o.hb_fused && bn_prepare && head_fused_on()) continue;               // the same in the stage-2 head trainer's passes
             const int rc = o.kind == gnet::K_CONV ? run_conv_fwd(o, train, s) : (o.kind == gnet::K_BN ? run_bn_fwd(o, train, s) : o.ffwd(train, s));
             if (rc) return rc;
         }

@@ -75,11 +75,16 @@ int GNet::load(const char* name_c, const void* tensor_, const int64_t* shape, in
 // meta-only mode: which eval-forward BatchNorm2d ride in their convolution's epilogue.  The BN must read the raw output of a matrix-core
 // convolution without an activation of its own, over the same passes, in one of the switch combinations the epilogue computes; and because
 // the fused launch runs at the BN's place in the list, nothing between the two may read that raw output or write one of the convolution's sources.
-void GNet::plan_eval_affine() {
-    for (int i = 0; i < (int)ops.size(); ++i) {
+// stage2: the same rules for the prefix [0, end) that the stage-2 head trainer runs under bn_prepare (Op::hb_from / hb_fused), with the two
+// residual forms the eval forward does not have: act_first (relu(relu(bn) + res)) and the plain residual (bn + res).  Every instantiation
+// these forms take, bf16x6 ones included, runs without scratch (profiles/head_bn_fused.txt), so none is held back.
+void GNet::plan_affine(int end, bool stage2) {
+    for (int i = 0; i < end && i < (int)ops.size(); ++i) {
         Op& b = ops[i];
-        if (b.kind != K_BN || b.tracked || b.train_only || b.act_first || (b.res >= 0 && !b.res_relu) || b.rH > 0) continue;
+        if (b.kind != K_BN || b.tracked || b.train_only || b.rH > 0) continue;
+        if (!stage2 && (b.act_first || (b.res >= 0 && !b.res_relu))) continue;
         if (b.act != GACT_NONE && b.act != GACT_RELU && b.act != GACT_LRELU) continue;
+        if (!ptta_gbn_switches_ok(b.res >= 0, b.act, b.res_relu ? 1 : 0, b.act_first ? 1 : 0)) continue;
         int k = i - 1;
         while (k >= 0 && !(ops[k].kind == K_CONV && ops[k].y == b.x[0])) --k;
         if (k < 0) continue;
@@ -93,7 +98,8 @@ void GNet::plan_eval_affine() {
             else for (int sidx = 0; sidx < c.nsrc; ++sidx) if (m.y == c.x[sidx]) clean = false;
         }
         if (!clean) continue;
-        b.aff_from = k; ops[k].aff_fused = true;
+        if (stage2) { b.hb_from = k; ops[k].hb_fused = true; }
+        else { b.aff_from = k; ops[k].aff_fused = true; }
     }
 }
 // the eval affine of every BatchNorm2d from its LOADED buffers (gbn_eval_affine_kernel: PTTA_GBN_EVAL's finalize); once per load()
@@ -105,6 +111,38 @@ int GNet::prepare_eval_affines(hipStream_t s) {
         if (ptta_launch_gbn_eval_affine(bn_gamma(o), bn_beta(o), o.rm_own, o.rv_own, BN_EPS, T[o.x[0]].C, o.st_eval, s)) return fail("batch-norm " + o.bname + " (eval affine) launch failed", -5);
         o.st_eval_valid = true;
     }
+    return 0;
+}
+
+// stage-2 head trainer, option "head_bn_fused": the eval affine of every fused BatchNorm2d of the prefix from the gamma / beta bound NOW and
+// the loaded running statistics, one launch per head_forward.  The entry table is uploaded again only when a pointer in it changed.
+int GNet::prepare_head_affines(hipStream_t s) {
+    if (!head_fused_on()) return 0;
+    hb_host.clear();
+    int maxC = 0;
+    for (int i = 0; i < head_bn_end && i < (int)ops.size(); ++i) {
+        const Op& o = ops[i];
+        if (o.kind != K_BN || o.hb_from < 0) continue;
+        if (!o.has_running) return fail("running statistics of " + o.bname + " not loaded (the stage-2 head trainer evaluates BatchNorm2d from them)", -3);
+        const int C = T[o.x[0]].C;
+        hb_host.push_back(GbnEvalEntry{bn_gamma(o), bn_beta(o), o.rm_own, o.rv_own, o.st_eval, (long)C});
+        if (C > maxC) maxC = C;
+        o.st_eval_valid = false;                 // (not the table another forward may take for its own: as the separate path leaves it)
+    }
+    const int n = (int)hb_host.size();
+    if (!n) return 0;
+    if (n > hb_tab_cap) {
+        GbnEvalEntry* tab = (GbnEvalEntry*)dalloc((size_t)n * sizeof(GbnEvalEntry));
+        if (!tab) return fail("out of device memory (head trainer affine table)", -12);
+        hb_tab = tab; hb_tab_cap = n; hb_sent.clear();
+    }
+    if (hb_sent.size() != hb_host.size() || memcmp(hb_sent.data(), hb_host.data(), (size_t)n * sizeof(GbnEvalEntry)) != 0) {
+        // (the stream may still read the last upload's source: the copy below is taken from hb_sent, which is replaced only after a wait)
+        NCHK(hipStreamSynchronize(s));
+        hb_sent = hb_host;
+        NCHK(hipMemcpyAsync(hb_tab, hb_sent.data(), (size_t)n * sizeof(GbnEvalEntry), hipMemcpyHostToDevice, s));
+    }
+    if (ptta_launch_gbn_eval_affine_multi(hb_tab, n, maxC, BN_EPS, s)) return fail("batch-norm eval affine tables (head trainer) launch failed", -5);
     return 0;
 }
 
@@ -130,6 +168,8 @@ int GNet::run_conv_fwd(const Op& o, bool train, hipStream_t s, const Op* aff) {
         if (aff) {          // y = act(fmaf(conv + bias, scale, shift) [+ res]): the BN's activation, or the BasicBlock's ReLU behind the sum
             a.scale = aff->st_eval + 2 * y.C; a.shift = aff->st_eval + 3 * y.C;
             a.act = aff->res >= 0 ? GACT_RELU : aff->act;
+            if (aff->res >= 0 && !aff->res_relu) { a.act = GACT_NONE; a.aff_res_plain = 1; }            // bn + res (the 2layers block)
+            else if (aff->res >= 0 && aff->act_first) a.aff_act_first = 1;                             // relu(relu(bn) + res) (CostDCNet's ResBlock)
             if (aff->res >= 0) { const GView r = view(aff->res, aff->xw[0], train); a.res = r.p; a.ld_res = r.ld; }
         }
         if (o.stat_to >= 0 && !(meta_only && !train) && (train || !ops[o.stat_to].tracked) && !(bn_prepare && !ops[o.stat_to].tracked) && !bn_eval_in_train(ops[o.stat_to])) {
@@ -167,6 +207,8 @@ int GNet::run_bn_fwd(const Op& o, bool train, hipStream_t s) {
     }
     if (bn_prepare && !o.tracked) {                         // stage-2 head trainer: a BatchNorm2d in eval mode, every pass from the loaded running statistics
         if (!o.has_running) return fail("running statistics of " + o.bname + " not loaded (the stage-2 head trainer evaluates BatchNorm2d from them)", -3);
+        // in the epilogue of its convolution, from the table prepare_head_affines built at the start of this head_forward
+        if (head_fused_on() && o.hb_from >= 0) return run_conv_fwd(ops[o.hb_from], train, s, &o);
         if (ptta_launch_gbn_eval_affine(bn_gamma(o), bn_beta(o), o.rm_own, o.rv_own, BN_EPS, x.C, o.st_eval, s)) return fail("batch-norm " + o.bname + " (prepare) launch failed", -5);
         o.st_eval_valid = false;
         if (ptta_launch_gbn_apply(x, res, y, 1, o.act, o.st_eval, o.res_relu ? 1 : 0, s, o.act_first ? 1 : 0)) return fail("batch-norm " + o.bname + " (prepare) launch failed", -5);

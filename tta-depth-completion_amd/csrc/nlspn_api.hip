@@ -225,6 +225,7 @@ struct nlspn_engine : GNet {
 
         plan_backward({t_pred, t_oa, t_conf, t_ref});           // written by the propagation / loss gradients
         if (meta_only) plan_eval_affine();
+        plan_head_affine(enc_ops_end);                         // stage-2 head trainer: conv1 .. conv6 (head_features)
         // ---- remaining workspace ----
         const long P = (long)H * W;
         off9 = falloc((size_t)N * P * 18); aff9 = falloc((size_t)N * P * 9);

@@ -456,7 +456,15 @@ int ptta_set_option(ptta_handle c, const char* key, int value) {
         if (c->nl->eval_bn_fused != value) { c->nl->drop_graphs(); c->nl->eval_bn_fused = value; }
         return 0;
     }
-    if (c->nl) return -38;                         // the generic engine has the one switch besides
+    if (k == "head_bn_fused" || k == "head_bn_fused_count") {   // NLSPN / CostDCNet: the stage-2 head trainer's frozen BatchNorm2d in the convolution epilogue
+        if (!c->nl) return c->fail("ptta_set_option: '" + k + "' belongs to the generic engine's handles (MSG_CHN has no BatchNorm2d)", -38);
+        c->err.clear();
+        if (k == "head_bn_fused_count") return c->nl->fail("ptta_set_option: 'head_bn_fused_count' is read-only", -22);
+        if (value < 0 || value > 1) return c->nl->fail("ptta_set_option: value out of range for 'head_bn_fused'", -22);
+        if (c->nl->head_bn_fused != value) { c->nl->drop_graphs(); c->nl->head_bn_fused = value; }
+        return 0;
+    }
+    if (c->nl) return -38;                         // the generic engine has no other switch
     const Option* o = find_option(k);
     if (!o) return c->fail("ptta_set_option: unknown key '" + k + "'", -22);
     int* f = &(c->*(o->member));
@@ -482,6 +490,11 @@ int ptta_get_option(ptta_handle c, const char* key, int* value) {
     // without the caller's stream (the second stream is created on first use)
     if (k == "thru_active") { *value = c->nl ? 0 : (c->thru && c->cos_grad_fused && heads_v2_on(c) && c->use_aux); return 0; }
     if (k == "eval_bn_fused") { if (!c->nl || !c->nl->meta_only) return -38; *value = c->nl->eval_bn_fused; return 0; }
+    if (k == "head_bn_fused" || k == "head_bn_fused_count") {
+        if (!c->nl) return -38;
+        *value = k == "head_bn_fused" ? c->nl->head_bn_fused : c->nl->head_bn_fused_count();
+        return 0;
+    }
     if (c->nl) { if (k != "graph") return -38; *value = c->nl->use_graph; return 0; }
     if (k == "graph") { *value = c->use_graph; return 0; }
     const Option* o = find_option(k);

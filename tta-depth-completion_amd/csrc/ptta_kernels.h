@@ -324,6 +324,9 @@ int ptta_launch_glinear_wgrad(const GView& x, const GView& gy, float* gw, float*
 int ptta_gbn_part_floats(int C, int npass);
 // the switch combinations the launchers below compute in both directions (they refuse the others with -22 before their first launch)
 bool ptta_gbn_switches_ok(bool has_res, int act, int res_relu, int act_first);
+// the eval affine tables [mean, inv, scale, shift][C] of a list of BatchNorms from their running statistics, one launch (device table of entries)
+struct GbnEvalEntry { const float *gamma, *beta, *rm, *rv; float* st; long C; };     // (no padding: tables are compared bytewise)
+int ptta_launch_gbn_eval_affine_multi(const GbnEvalEntry* tab_dev, int n, int max_C, float eps, hipStream_t s);
 int ptta_launch_gbn_forward(const GView& x, const GView& res, const GView& y, int npass, int act, float eps, const float* gamma,
                             const float* beta, float* part, float* st, hipStream_t s, int fused_blocks = 0, int act_first = 0,
                             const PttaStatSync* sync = nullptr,
@@ -375,11 +378,17 @@ struct GX3Args {
     //   y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res])   -- the arithmetic of gbn_apply_kernel, bit for bit
     // not with accumulate, the fused statistics or the sigmoid (the launchers return -22)
     const float* scale = nullptr; const float* shift = nullptr; const float* res = nullptr; int ld_res = 0;
+    // the two other residual forms of gbn_apply_kernel behind the affine (the stage-2 head trainer's frozen BatchNorm2d):
+    //   aff_act_first: y = relu(relu(fmaf(..)) + res)   -- CostDCNet's ResBlock (Op::act_first); act = GACT_RELU, instantiations of their own
+    //   aff_res_plain: y = fmaf(..) + res                -- the 2layers block's last BatchNorm2d (Op::res_relu = false); act = GACT_NONE
+    int aff_act_first = 0, aff_res_plain = 0;
 };
-// the affine epilogue's own argument rules, checked by both launchers before their launch
+// the affine epilogue's own argument rules, checked by both launchers before their launch: what ptta_gbn_switches_ok refuses is refused here
 inline bool ptta_gx3_affine_ok(const GX3Args& a) {
-    if (!a.scale && !a.shift && !a.res) return true;
+    if (!a.scale && !a.shift && !a.res && !a.aff_act_first && !a.aff_res_plain) return true;
     if (!a.scale || !a.shift || a.accumulate || a.stat_part || (a.act != GACT_NONE && a.act != GACT_RELU && a.act != GACT_LRELU)) return false;
+    if (a.aff_act_first && (a.aff_res_plain || !a.res || a.act != GACT_RELU || a.vert)) return false;
+    if (a.aff_res_plain && (!a.res || a.act != GACT_NONE)) return false;
     return !a.res || a.ld_res >= a.Cy;
 }
 void ptta_gfrag_pack(const float* canon, long wld, long wts, int KK, int C0, int C1, int c0_0, int c0_1, int Co, bf16_t* hi, bf16_t* lo,

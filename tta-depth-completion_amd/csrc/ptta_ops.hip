@@ -153,13 +153,18 @@ static int op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, i
     if (affine) {
         const int cm = geom == PTTA_GCONV_S1 ? 7 : 15;          // channel counts the matrix-core forms take (ptta_launch_gconv_x3 / _strided)
         if (!scale || !shift || (((size_t)scale | (size_t)shift) & 15) || (res != nullptr) != (ld_res != 0) || (res && ld_res < co) ||
-            impl != 0 || accumulate || stat_npass || six_b || (flags & PTTA_GCONV_DGRAD) || (act != GACT_NONE && act != GACT_RELU && act != GACT_LRELU) ||
+            impl != 0 || accumulate || stat_npass || six_b < 0 || six_b > b || (flags & PTTA_GCONV_DGRAD) || (act != GACT_NONE && act != GACT_RELU && act != GACT_LRELU) ||
             c0 < 1 || c1 < 0 || (c0 & cm) || (c1 & cm)) return -22;
-    }
+        // the residual forms, as ptta_gbn_switches_ok has them: act_first takes a residual and ReLU, the plain residual no activation
+        const bool af = flags & PTTA_GCONV_AFF_ACT_FIRST, rp = flags & PTTA_GCONV_AFF_RES_PLAIN;
+        if ((af && rp) || (af && (!res || act != GACT_RELU || (flags & PTTA_GCONV_VERT))) || (rp && (!res || act != GACT_NONE))) return -22;
+        // the transposed geometry has the plain bf16x3 epilogue only (ptta_launch_gconv_x3_strided)
+        if (geom == PTTA_GCONV_T2 && (af || six_b > 0)) return -22;
+    } else if (flags & (PTTA_GCONV_AFF_ACT_FIRST | PTTA_GCONV_AFF_RES_PLAIN)) return -22;
     const bool vert = flags & PTTA_GCONV_VERT, dgrad = flags & PTTA_GCONV_DGRAD;
     if (!x0 || !weight || !y || b < 1 || hin < 1 || win < 1 || hout < 1 || wout < 1 || c0 < 1 || c1 < 0 || co < 1 || ld0 < c0 || ldy < co ||
         (c1 > 0) != (x1 != nullptr) || (c1 > 0 && ld1 < c1) || (k != 1 && k != 3) || geom < PTTA_GCONV_S1 || geom > PTTA_GCONV_T2 ||
-        act < GACT_NONE || act > GACT_SIGMOID || impl < 0 || impl > 1 || (flags & ~7) || six_b < 0 || six_b > b || x1_from_b < 0 ||
+        act < GACT_NONE || act > GACT_SIGMOID || impl < 0 || impl > 1 || (flags & ~31) || six_b < 0 || six_b > b || x1_from_b < 0 ||
         stat_npass < 0 || stat_npass > 2 || (accumulate & ~1)) return -22;
     if (vert && (k != 3 || geom != PTTA_GCONV_S1)) return -22;
     if (dgrad && (c1 > 0 || six_b > 0)) return -22;
@@ -209,7 +214,10 @@ static int op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, i
             if (six_b > 0) { a.wl2 = (const uint4*)cw.ff_l2; a.six_B = six_b; }
             a.x1_from_B = x1_from_b; a.x1_w2 = (flags & PTTA_GCONV_X1_W2) ? 1 : 0;
             if (stat) { a.stat_part = stat; a.stat_C = co; a.stat_npass = stat_npass; }
-            if (affine) { a.scale = scale; a.shift = shift; a.res = res; a.ld_res = ld_res; }
+            if (affine) {
+                a.scale = scale; a.shift = shift; a.res = res; a.ld_res = ld_res;
+                a.aff_act_first = (flags & PTTA_GCONV_AFF_ACT_FIRST) ? 1 : 0; a.aff_res_plain = (flags & PTTA_GCONV_AFF_RES_PLAIN) ? 1 : 0;
+            }
             if (run == PTTA_GCONV_S1) rc = ptta_launch_gconv_x3(a, k, s);
             else {
                 const int mode = run == PTTA_GCONV_T2 ? 2 : 1;
@@ -257,7 +265,8 @@ int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int
     return op_gconv(x0, c0, ld0, x1, c1, ld1, weight, bias, y, co, ldy, b, hin, win, hout, wout, k, geom, act, accumulate, impl, flags, six_b, x1_from_b,
                     stat_npass, stat_host, form_host, false, nullptr, nullptr, nullptr, 0, s_);
 }
-// the same convolution with the eval-BatchNorm epilogue of the meta-only mode: y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res])
+// the same convolution with the eval-BatchNorm epilogue (the meta-only eval forward, the stage-2 head trainer): y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res])
+// and, by flag, relu(relu(fmaf(..)) + res) or fmaf(..) + res
 int ptta_op_gconv_affine(const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, const float* weight, const float* bias, float* y, int co,
                          int ldy, int b, int hin, int win, int hout, int wout, int k, int geom, int act, int accumulate, int impl, int flags,
                          int six_b, int x1_from_b, int stat_npass, double* stat_host, int* form_host, const float* scale, const float* shift,

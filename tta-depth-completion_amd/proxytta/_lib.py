@@ -26,6 +26,12 @@ PTTA_DTYPE_F32 = 0
 PTTA_DTYPE_MIXED = 1
 PTTA_HEAD_FORM_PLAIN = 0
 PTTA_HEAD_FORM_SYNCBN = 1
+# ptta_op_gconv / ptta_op_gconv_affine `flags`
+PTTA_GCONV_VERT = 1
+PTTA_GCONV_X1_W2 = 2
+PTTA_GCONV_DGRAD = 4
+PTTA_GCONV_AFF_ACT_FIRST = 8
+PTTA_GCONV_AFF_RES_PLAIN = 16
 PTTA_ABI_VERSION = 2           # include/ptta.h; checked against ptta_version() at load
 CONV_S1, CONV_S2, CONV_T2 = 0, 1, 2
 

@@ -452,7 +452,7 @@ class Engine:
 
     def set_option(self, key, value):
         """Per-handle switch (include/ptta.h ptta_set_option: graph, aux_stream, thru, fuse_first, fuse_head_bwd, fuse_heads, heads_v2,
-        cos_in_gemm, mask_bits, stamps)."""
+        cos_in_gemm, mask_bits, stamps; eval_bn_fused, head_bn_fused on the generic engine's handles)."""
         self._chk(self.lib.ptta_set_option(self.handle, key.encode(), int(value)), 'ptta_set_option(%s)' % key)
 
     def get_option(self, key):
@@ -552,10 +552,11 @@ def op_gconv(x0, weight, y, x1=None, bias=None, k=3, geom='s1', act='none', accu
 
 
 def op_gconv_affine(x0, weight, y, scale, shift, x1=None, bias=None, res=None, ld_res=None, k=3, geom='s1', act='none', impl='mfma',
-                    accumulate=False):
-    """Test hook: op_gconv with the eval-BatchNorm epilogue of NLSPN's meta-only mode (include/ptta.h ptta_op_gconv_affine):
-    y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res]).  scale / shift [co] device tensors; res [b, hout, wout, co], possibly a channel
-    slice of a wider tensor; ld_res overrides the residual's pixel stride (the argument checks).  Returns the strided launch form."""
+                    accumulate=False, act_first=False, res_plain=False, six_b=0):
+    """Test hook: op_gconv with the eval-BatchNorm epilogue of NLSPN's meta-only mode and of the stage-2 head trainer (include/ptta.h
+    ptta_op_gconv_affine): y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res]); act_first: relu(relu(fmaf(..)) + res); res_plain:
+    fmaf(..) + res.  scale / shift [co] device tensors; res [b, hout, wout, co], possibly a channel slice of a wider tensor; ld_res
+    overrides the residual's pixel stride (the argument checks); six_b: the images below it in bf16x6.  Returns the strided launch form."""
     lib = _lib.load()
 
     def view(t):
@@ -571,7 +572,9 @@ def op_gconv_affine(x0, weight, y, scale, shift, x1=None, bias=None, res=None, l
     pr, _, ldr = view(res) if res is not None else (None, 0, 0)
     form = c_int(-1)
     rc = lib.ptta_op_gconv_affine(p0, c0, ld0, p1, c1, ld1, ptr(weight.contiguous()), ptr(bias), py, co, ldy, b, hin, win, hout, wout, k,
-                                  GCONV_GEOMS[geom], GCONV_ACTS[act], int(bool(accumulate)), GCONV_IMPLS[impl], 0, 0, 1 << 30, 0, None,
+                                  GCONV_GEOMS[geom], GCONV_ACTS[act], int(bool(accumulate)), GCONV_IMPLS[impl],
+                                  (_lib.PTTA_GCONV_AFF_ACT_FIRST if act_first else 0) | (_lib.PTTA_GCONV_AFF_RES_PLAIN if res_plain else 0),
+                                  int(six_b), 1 << 30, 0, None,
                                   byref(form), ptr(scale), ptr(shift), pr, ldr if ld_res is None else int(ld_res), _stream())
     if rc != 0:
         raise RuntimeError('ptta_op_gconv_affine failed (%d)' % rc)
