@@ -578,6 +578,74 @@ typedef struct ptta_gbn_args {
     float* st; float* rm; float* rv; long long* nbt; float* st_eval; float* dgamma; float* dbeta;
 } ptta_gbn_args;
 int ptta_op_gbn(const ptta_gbn_args* a, ptta_stream s);
+/* Test hooks: CostDCNet's own kernels (csrc/costdc_kernels.hip) on caller-supplied device buffers, launched through the launchers of
+ * csrc/costdc.h exactly as the engine (csrc/costdc_api.hip) launches them.  All of them synchronise; -22 BEFORE any launch for arguments
+ * the kernels would index out of bounds with, -12 out of memory, -5 a HIP error.
+ *
+ * ptta_cd_sparse: the sparse voxel sets of the 3-D encoder for n frames of h x w pixels (h, w multiples of 4: level l has tensor stride
+ * (1, 1 << l, 1 << l)), with the scratch the engine gives them.  _build: depth2MDP of `sparse` [n][h][w] (device) and the two coarser
+ * levels.  _read: cnt_host [3] voxel counts; of `level`: coords_host [min(cnt, coords_cap)][4] = (frame, plane, y, x), vol_host
+ * [n][16][h >> level][w >> level] (voxel id or -1) and, level 0 only, feat_in_host [min(cnt, coords_cap)]; NULL skips an output. */
+typedef struct ptta_cd_sparse ptta_cd_sparse;
+int ptta_cd_sparse_create(ptta_cd_sparse** out, int n, int h, int w);
+void ptta_cd_sparse_destroy(ptta_cd_sparse* q);
+int ptta_cd_sparse_build(ptta_cd_sparse* q, const float* sparse, float z_step, ptta_stream s);
+int ptta_cd_sparse_read(ptta_cd_sparse* q, int level, int* cnt_host, int* coords_host, long long coords_cap, int* vol_host, float* feat_in_host,
+                        ptta_stream s);
+/* Generalized sparse convolution from level lin to level lout (lout = lin or lin + 1: stride (1,2,2)), kernel (ksize^3, ci, co), ksize 1 or 3.
+ * backward = 0: x [cnt[lin]][ci] -> y [cnt[lout]][co] (co <= 64).  backward = 1: the transpose, x = dy [cnt[lout]][co] -> y = dx [cnt[lin]][ci]
+ * (ci <= 64), added to y when acc = 1. */
+int ptta_op_cd_sparse_conv(ptta_cd_sparse* q, const float* x, const float* wk, float* y, int lin, int lout, int ksize, int ci, int co, int backward,
+                           int acc, ptta_stream s);
+/* BatchNorm over the voxels of `level` (c <= 64 channels), mode as ptta_op_gbn's.
+ *   PTTA_GBN_TRAIN     f, optional res -> out = relu?(bn(f) + res?) and st [4][c] = {scale, shift, mean, inv}; rm != NULL (with rv; nbt
+ *                      optional): running statistics updated `repeats` times (momentum 0.1, unbiased variance).
+ *   PTTA_GBN_EVAL      the same from rm / rv.
+ *   PTTA_GBN_BACKWARD  f, y (the forward's output), g, st -> gx, dgamma, dbeta and optional gres (written, or added to when acc_res = 1).
+ * world > 1: the stand-in collective of ptta_op_gbn (train and backward). */
+typedef struct ptta_cd_sbn_args {
+    int mode, level, c, relu, repeats, world, acc_res;
+    const float* f; const float* res; const float* y; const float* g; const float* gamma; const float* beta;
+    float* rm; float* rv; long long* nbt; float* out; float* st; float* dgamma; float* dbeta; float* gx; float* gres;
+} ptta_cd_sbn_args;
+int ptta_op_cd_sbn(ptta_cd_sparse* q, const ptta_cd_sbn_args* a, ptta_stream s);
+/* backward = 0: in [cnt[2]][c] -> out [n][16][h/4][w/4][c] (zero elsewhere).  backward = 1: in = the gradient volume with ldv channels per
+ * cell, out [cnt[2]][c] = its channels c0 .. c0 + c - 1 at the level-2 voxels. */
+int ptta_op_cd_densify(ptta_cd_sparse* q, const float* in, float* out, int c, int backward, int ldv, int c0, ptta_stream s);
+/* The dense kernels.  d = integer arguments, f = float arguments {div, mean[3], std[3]} or {z_step} or {max depth}; a, b inputs, out, out2
+ * outputs (NHWC / NDHWC as csrc/costdc_kernels.hip states them):
+ *   PAD_DUAL          d {N, C, H, W, Hp, Wp, pt, pr, norm}     a [N][C][H][W] -> out [2N][C][Hp][Wp]; norm = 1 (C = 3) normalises in-frame pixels
+ *   CROP_AVG          d {N, H, W, Hp, Wp, pt, pr}              a [2N][Hp][Wp] -> out [N][H][W]   (H + pt <= Hp, W + pr <= Wp)
+ *   SCATTER_DUAL_GRAD d {N, H, W, Hp, Wp, pt, pr}              a [N][H][W] -> out [2N][Hp][Wp]
+ *   STAGE             d {N, passes, H, W, C, norm}             a image [N][3][H][W], b sparse [N][H][W] -> out [passes N][H][W][C], C 4 or 16
+ *   CLAMP             d {n}, f {max depth}                     a -> out
+ *   FUSION_FWD        d {N, passes, h, w}                      a feat2d [passes N][h][w][16], b feat3d [N][16][h][w][16] -> out [passes N][16][h][w][32], out2 mask [N][16][h][w]
+ *   FUSION_BWD        d {N, h, w}                              a gvol [N][16][h][w][32], b mask -> out [N][h][w][16]
+ *   POOL_FWD          d {items_out, H, W, C}                   a [2 items_out][H][W][C] -> out [items_out][H/2][W/2][C], C % 4 == 0
+ *   POOL_BWD          d {items_in, H, W, C, acc}               a x, b gy -> out gx; items_in even
+ *   UP_FWD            d {frames, Di, Hi, Wi, Do, Ho, Wo, C}    a -> out, C % 4 == 0
+ *   UP_BWD            d {frames, Di, Hi, Wi, Do, Ho, Wo, C, acc}  a gy -> out gx
+ *   REGRESS_FWD       d {N, h, w}, f {z_step}                  a cost [N][16][h][w][16] -> out [N][4h][4w]
+ *   REGRESS_BWD       d {N, h, w}, f {z_step}                  a cost, b gpred -> out gcost
+ *   ROWS_FWD          d {N, D, h, w, C}                        a [N][D][h][w][C] -> out [N h w][C D]
+ *   ROWS_BWD          d {N, D, h, w, C, acc}                   a grows -> out gfeat
+ * Buffers a kernel reads or writes as float4 must be 16-byte aligned. */
+#define PTTA_CD_PAD_DUAL 0
+#define PTTA_CD_CROP_AVG 1
+#define PTTA_CD_SCATTER_DUAL_GRAD 2
+#define PTTA_CD_STAGE 3
+#define PTTA_CD_CLAMP 4
+#define PTTA_CD_FUSION_FWD 5
+#define PTTA_CD_FUSION_BWD 6
+#define PTTA_CD_POOL_FWD 7
+#define PTTA_CD_POOL_BWD 8
+#define PTTA_CD_UP_FWD 9
+#define PTTA_CD_UP_BWD 10
+#define PTTA_CD_REGRESS_FWD 11
+#define PTTA_CD_REGRESS_BWD 12
+#define PTTA_CD_ROWS_FWD 13
+#define PTTA_CD_ROWS_BWD 14
+int ptta_op_cd_dense(int op, const float* a, const float* b, float* out, float* out2, const int* d, const float* f, ptta_stream s);
 /* Diagnostic (tools/bench_chain.py): `reps` dependent launches of one stride-1 32->32 convolution (fp32 NHWC, default arithmetic) captured
  * into one hipGraph and replayed `replays` times: microseconds per launch INSIDE a replayed graph.  epi_flags: 2 = ReLU mask from `aux`,
  * 4 = skip addition of `aux`, 8 = the same chain launched directly (no graph), 16 = the layer loop (ONE launch per `reps` layers with a

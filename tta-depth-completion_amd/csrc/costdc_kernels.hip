@@ -80,8 +80,9 @@ __global__ void cd_clamp_kernel(const float* __restrict__ src, float* __restrict
 
 // ---- sparse voxel sets ---------------------------------------------------------------------------------------------------
 // level l holds voxels (frame, plane z, y, x) whose y, x are multiples of ts = 1 << l (tensor stride (1, ts, ts)); `vol` is
-// the dense index volume [N][16][H >> l][W >> l] (-1 = empty); points are numbered in (frame, plane, row, column) order by a
-// row count + scan + fill, so every reduction over points has a fixed order.
+// the dense index volume [N][16][H >> l][W >> l] (-1 = empty); points are numbered by a row count + scan + fill, so every reduction
+// over points has a fixed order: level 0 in (frame, row, column) order (one voxel per pixel, whatever its plane), the coarser
+// levels in (frame, plane, row, column) order.
 __device__ __forceinline__ int cd_plane_of(float d, float z_step) { int z = (int)rintf(d / z_step); return z < 0 ? 0 : (z > 15 ? 15 : z); }
 // one wave per image row: lanes stride over the columns, ballot + popcount
 __global__ __launch_bounds__(256) void cd_l0_rowcount_kernel(const float* __restrict__ sparse, int N, int H, int W, float z_step, int* __restrict__ rowcnt) {

@@ -1,7 +1,9 @@
 // Entry points that take no handle: outlier removal, evaluation metrics, the modulated deformable convolution, and the
-// stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_gconv, ptta_op_gconv_affine, ptta_op_gbn, ptta_op_conv32_chain).
+// stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_gconv, ptta_op_gconv_affine, ptta_op_gbn, ptta_op_conv32_chain,
+// and CostDCNet's own kernels: ptta_cd_sparse_*, ptta_op_cd_sparse_conv, ptta_op_cd_sbn, ptta_op_cd_densify, ptta_op_cd_dense).
 #include "msgchn_ctx.h"
 #include "gnet.h"
+#include "costdc.h"
 
 using namespace msgchn;
 
@@ -332,6 +334,177 @@ int ptta_op_gbn(const ptta_gbn_args* a, ptta_stream s_) {
     }
     if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
     (void)hipFree(part); (void)hipFree(bw); (void)hipFree(xbuf);
+    return rc;
+}
+
+// ---- CostDCNet's own kernels (costdc_kernels.hip) on caller-supplied device buffers (tests): every hook calls the launchers of costdc.h
+// as costdc_api.hip calls them.  include/ptta.h states the arguments.
+struct ptta_cd_sparse {
+    CdSparse q;
+    long cap = 0;
+    ~ptta_cd_sparse() {
+        for (int l = 0; l < 3; ++l) { (void)hipFree(q.vol[l]); (void)hipFree(q.coords[l]); }
+        (void)hipFree(q.cnt); (void)hipFree(q.rowcnt); (void)hipFree(q.rowoff); (void)hipFree(q.feat_in); (void)hipFree(q.bn_part); (void)hipFree(q.bn_st);
+    }
+};
+// sized as costdc_engine::build_sparse() sizes it
+int ptta_cd_sparse_create(ptta_cd_sparse** out, int n, int h, int w) {
+    if (!out) return -22;
+    *out = nullptr;
+    if (n < 1 || h < 4 || w < 4 || (h & 3) || (w & 3) || (long)n * 16 * h * w > 0x7fffffffL) return -22;   // level 2 halves twice; the row kernels index with int
+    ptta_cd_sparse* p = new ptta_cd_sparse();
+    CdSparse& q = p->q;
+    q.N = n; q.H = h; q.W = w; p->cap = (long)n * h * w;
+    bool ok = true;
+    for (int l = 0; l < 3 && ok; ++l)
+        ok = hipMalloc((void**)&q.vol[l], (size_t)n * 16 * (h >> l) * (w >> l) * sizeof(int)) == hipSuccess &&
+             hipMalloc((void**)&q.coords[l], (size_t)p->cap * sizeof(int4)) == hipSuccess;
+    ok = ok && hipMalloc((void**)&q.cnt, 4 * sizeof(int)) == hipSuccess && hipMemset(q.cnt, 0, 4 * sizeof(int)) == hipSuccess &&
+         hipMalloc((void**)&q.rowcnt, (size_t)n * 16 * h * sizeof(int)) == hipSuccess && hipMalloc((void**)&q.rowoff, (size_t)n * 16 * h * sizeof(int)) == hipSuccess &&
+         hipMalloc((void**)&q.feat_in, (size_t)p->cap * sizeof(float)) == hipSuccess && hipMalloc((void**)&q.bn_part, (size_t)256 * 2 * 64 * sizeof(float)) == hipSuccess &&
+         hipMalloc((void**)&q.bn_st, 4 * 64 * sizeof(float)) == hipSuccess;
+    if (!ok) { delete p; return -12; }
+    *out = p;
+    return 0;
+}
+void ptta_cd_sparse_destroy(ptta_cd_sparse* p) { delete p; }
+int ptta_cd_sparse_build(ptta_cd_sparse* p, const float* sparse, float z_step, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!p || !sparse || !(z_step > 0.f)) return -22;
+    int rc = cd_sparse_levels_build(p->q, sparse, z_step, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+int ptta_cd_sparse_read(ptta_cd_sparse* p, int level, int* cnt_host, int* coords_host, long long coords_cap, int* vol_host, float* feat_in_host, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!p || level < 0 || level > 2 || coords_cap < 0 || (feat_in_host && level != 0) || ((coords_host || feat_in_host) && coords_cap < 1)) return -22;
+    const CdSparse& q = p->q;
+    int cnt[3];
+    if (hipMemcpyAsync(cnt, q.cnt, 3 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return -5;
+    if (cnt_host) for (int l = 0; l < 3; ++l) cnt_host[l] = cnt[l];
+    long long rows = cnt[level] < 0 ? 0 : cnt[level];
+    if (rows > coords_cap) rows = coords_cap;
+    if (rows > p->cap) rows = p->cap;
+    int rc = 0;
+    if (coords_host && rows && hipMemcpyAsync(coords_host, q.coords[level], (size_t)rows * sizeof(int4), hipMemcpyDeviceToHost, s) != hipSuccess) rc = -5;
+    if (!rc && feat_in_host && rows && hipMemcpyAsync(feat_in_host, q.feat_in, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) rc = -5;
+    if (!rc && vol_host &&
+        hipMemcpyAsync(vol_host, q.vol[level], (size_t)q.N * 16 * (q.H >> level) * (q.W >> level) * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+int ptta_op_cd_sparse_conv(ptta_cd_sparse* p, const float* x, const float* wk, float* y, int lin, int lout, int ksize, int ci, int co, int backward, int acc,
+                           ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!p || !x || !wk || !y || lin < 0 || lout < lin || lout > 2 || lout - lin > 1 || (ksize != 1 && ksize != 3) || ci < 1 || co < 1 || (backward & ~1) || (acc & ~1) ||
+        (!backward && acc) || (backward ? ci : co) > 64) return -22;
+    int rc = backward ? cd_launch_sparse_conv_bwd(p->q, x, lin, lout, wk, ksize, ci, co, y, acc, s) : cd_launch_sparse_conv(p->q, x, lin, lout, wk, ksize, ci, co, y, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+int ptta_op_cd_sbn(ptta_cd_sparse* p, const ptta_cd_sbn_args* a, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!p || !a || a->mode < PTTA_GBN_TRAIN || a->mode > PTTA_GBN_BACKWARD || a->level < 0 || a->level > 2 || a->c < 1 || a->c > 64 || (a->relu & ~1) ||
+        (a->acc_res & ~1) || a->world < 1 || !a->f || !a->gamma || !a->st) return -22;
+    const bool bwd = a->mode == PTTA_GBN_BACKWARD, train = a->mode == PTTA_GBN_TRAIN;
+    if (!bwd && (!a->beta || !a->out || (a->rm != nullptr) != (a->rv != nullptr) || (!train && !a->rm) || (train && a->rm && a->repeats < 1) || (!train && a->world > 1)))
+        return -22;
+    if (bwd && (!a->y || !a->g || !a->gx || !a->dgamma || !a->dbeta)) return -22;
+    const int C = a->c;
+    int world = a->world, rc = 0;
+    double* xbuf = nullptr; float* bw = nullptr;
+    if (world > 1 && hipMalloc((void**)&xbuf, (size_t)(2 * C + 1) * sizeof(double)) != hipSuccess) rc = -12;
+    if (!rc && bwd && hipMalloc((void**)&bw, (size_t)3 * 64 * sizeof(float)) != hipSuccess) rc = -12;
+    PttaStatSync sy;
+    if (world > 1) { sy.fn = op_gbn_exchange; sy.user = &world; sy.buf = xbuf; sy.cap = 2 * C + 1; sy.world = world; }
+    if (!rc) {
+        if (!bwd)
+            rc = cd_launch_sparse_bn(p->q, a->f, a->res, a->level, C, a->gamma, a->beta, a->rm, a->rv, a->rm ? a->nbt : nullptr, train ? 1 : 0, a->repeats, a->relu, a->out,
+                                     s, &sy, a->st);
+        else
+            rc = cd_launch_sparse_bn_bwd(p->q, a->f, a->y, a->g, a->level, C, a->gamma, a->st, a->relu, a->dgamma, a->dbeta, a->gx, a->gres, a->acc_res, bw, s, &sy);
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    (void)hipFree(xbuf); (void)hipFree(bw);
+    return rc;
+}
+int ptta_op_cd_densify(ptta_cd_sparse* p, const float* in, float* out, int c, int backward, int ldv, int c0, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!p || !in || !out || c < 1 || (backward & ~1) || (backward && (c0 < 0 || ldv < c0 + c))) return -22;
+    int rc = backward ? cd_launch_densify_bwd(p->q, in, ldv, c0, c, out, s) : cd_launch_densify(p->q, in, c, out, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+int ptta_op_cd_dense(int op, const float* a, const float* b, float* out, float* out2, const int* d, const float* f, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!a || !out || !d || op < PTTA_CD_PAD_DUAL || op > PTTA_CD_ROWS_BWD) return -22;
+    auto pos = [&](int k0, int k1) { for (int k = k0; k < k1; ++k) if (d[k] < 1) return false; return true; };
+    auto al16 = [](const void* q) { return !((size_t)q & 15); };
+    int rc = -22;
+    switch (op) {
+    case PTTA_CD_PAD_DUAL: {             // d = {N, C, H, W, Hp, Wp, pt, pr, norm}; f = {div, mean[3], std[3]}
+        if (!pos(0, 6) || d[6] < 0 || d[7] < 0 || (d[8] & ~1) || (d[8] && (d[1] != 3 || !f))) break;
+        rc = cd_launch_pad_dual(a, out, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], s, d[8], d[8] ? f[0] : 1.f, d[8] ? f + 1 : nullptr, d[8] ? f + 4 : nullptr);
+        break; }
+    case PTTA_CD_CROP_AVG:               // d = {N, H, W, Hp, Wp, pt, pr}: reads rows y + pt and columns x + pr of the padded frame
+        if (!pos(0, 5) || d[5] < 0 || d[6] < 0 || d[1] + d[5] > d[3] || d[2] + d[6] > d[4]) break;
+        rc = cd_launch_crop_avg(a, out, d[0], d[1], d[2], d[3], d[4], d[5], d[6], s);
+        break;
+    case PTTA_CD_SCATTER_DUAL_GRAD:      // d = {N, H, W, Hp, Wp, pt, pr}
+        if (!pos(0, 5) || d[5] < 0 || d[6] < 0) break;
+        rc = cd_launch_scatter_dual_grad(a, out, d[0], d[1], d[2], d[3], d[4], d[5], d[6], s);
+        break;
+    case PTTA_CD_STAGE:                  // d = {N, passes, H, W, C, norm}; f = {div, mean[3], std[3]} (read even when norm = 0)
+        if (!b || !f || !pos(0, 4) || d[1] > 2 || (d[4] != 4 && d[4] != 16) || (d[5] & ~1) || !al16(out)) break;
+        rc = cd_launch_stage(a, b, out, d[0], d[1], d[2], d[3], d[4], d[5], f[0], f + 1, f + 4, s);
+        break;
+    case PTTA_CD_CLAMP:                  // d = {n}; f = {max depth (< 0: copy)}
+        if (!f || d[0] < 1) break;
+        rc = cd_launch_clamp(a, out, (long)d[0], f[0], s);
+        break;
+    case PTTA_CD_FUSION_FWD:             // d = {N, passes, h, w}
+        if (!b || !out2 || !pos(0, 4) || d[1] > 2 || !al16(a) || !al16(b) || !al16(out)) break;
+        rc = cd_launch_fusion_fwd(a, b, out, out2, d[0], d[1], d[2], d[3], s);
+        break;
+    case PTTA_CD_FUSION_BWD:             // d = {N, h, w}
+        if (!b || !pos(0, 3)) break;
+        rc = cd_launch_fusion_bwd(a, b, out, d[0], d[1], d[2], s);
+        break;
+    case PTTA_CD_POOL_FWD:               // d = {items_out, H, W, C}: reads 2 items_out planes
+        if (!pos(0, 4) || (d[3] & 3) || !al16(a) || !al16(out)) break;
+        rc = cd_launch_pool_fwd(a, out, (long)d[0], d[1], d[2], d[3], s);
+        break;
+    case PTTA_CD_POOL_BWD:               // d = {items_in, H, W, C, acc}: plane pairs, so items_in is even
+        if (!b || !pos(0, 4) || (d[0] & 1) || (d[4] & ~1)) break;
+        rc = cd_launch_pool_bwd(a, b, out, (long)d[0], d[1], d[2], d[3], d[4], s);
+        break;
+    case PTTA_CD_UP_FWD:                 // d = {frames, Di, Hi, Wi, Do, Ho, Wo, C}
+        if (!pos(0, 8) || (d[7] & 3) || !al16(a) || !al16(out)) break;
+        rc = cd_launch_up_fwd(a, out, (long)d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], s);
+        break;
+    case PTTA_CD_UP_BWD:                 // d = {frames, Di, Hi, Wi, Do, Ho, Wo, C, acc}
+        if (!pos(0, 8) || (d[8] & ~1)) break;
+        rc = cd_launch_up_bwd(a, out, (long)d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], s);
+        break;
+    case PTTA_CD_REGRESS_FWD:            // d = {N, h, w}; f = {z_step}
+        if (!f || !pos(0, 3)) break;
+        rc = cd_launch_regress_fwd(a, out, d[0], d[1], d[2], f[0], s);
+        break;
+    case PTTA_CD_REGRESS_BWD:
+        if (!b || !f || !pos(0, 3)) break;
+        rc = cd_launch_regress_bwd(a, b, out, d[0], d[1], d[2], f[0], s);
+        break;
+    case PTTA_CD_ROWS_FWD:               // d = {N, D, h, w, C}
+        if (!pos(0, 5)) break;
+        rc = cd_launch_rows_fwd(a, out, d[0], d[1], d[2], d[3], d[4], s);
+        break;
+    case PTTA_CD_ROWS_BWD:               // d = {N, D, h, w, C, acc}
+        if (!pos(0, 5) || (d[5] & ~1)) break;
+        rc = cd_launch_rows_bwd(a, out, d[0], d[1], d[2], d[3], d[4], d[5], s);
+        break;
+    }
+    if (rc == -22) return rc;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
     return rc;
 }
 

@@ -53,6 +53,15 @@ class GbnArgs(ctypes.Structure):               # include/ptta.h ptta_gbn_args
                 [(n, c_void_p) for n in ('gamma', 'beta', 'part_in', 'st', 'rm', 'rv', 'nbt', 'st_eval', 'dgamma', 'dbeta')])
 
 
+class CdSbnArgs(ctypes.Structure):             # include/ptta.h ptta_cd_sbn_args
+    _fields_ = ([(n, c_int) for n in ('mode', 'level', 'c', 'relu', 'repeats', 'world', 'acc_res')] +
+                [(n, c_void_p) for n in ('f', 'res', 'y', 'g', 'gamma', 'beta', 'rm', 'rv', 'nbt', 'out', 'st', 'dgamma', 'dbeta', 'gx', 'gres')])
+
+
+# ptta_op_cd_dense `op`
+CD_OPS = {'pad_dual': 0, 'crop_avg': 1, 'scatter_dual_grad': 2, 'stage': 3, 'clamp': 4, 'fusion_fwd': 5, 'fusion_bwd': 6, 'pool_fwd': 7,
+          'pool_bwd': 8, 'up_fwd': 9, 'up_bwd': 10, 'regress_fwd': 11, 'regress_bwd': 12, 'rows_fwd': 13, 'rows_bwd': 14}
+
 # every symbol include/ptta.h declares: (name, restype, argtypes)
 _P = c_void_p
 SIGNATURES = [
@@ -125,6 +134,14 @@ SIGNATURES = [
     ('ptta_op_gconv_affine', c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, _P, _P] + [c_int] * 16 + [POINTER(ctypes.c_double), POINTER(c_int),
                                      _P, _P, _P, c_int, _P]),
     ('ptta_op_gbn', c_int, [POINTER(GbnArgs), _P]),
+    ('ptta_cd_sparse_create', c_int, [POINTER(c_void_p), c_int, c_int, c_int]),
+    ('ptta_cd_sparse_destroy', None, [_P]),
+    ('ptta_cd_sparse_build', c_int, [_P, _P, c_float, _P]),
+    ('ptta_cd_sparse_read', c_int, [_P, c_int, POINTER(c_int), _P, ctypes.c_longlong, _P, _P, _P]),
+    ('ptta_op_cd_sparse_conv', c_int, [_P, _P, _P, _P] + [c_int] * 7 + [_P]),
+    ('ptta_op_cd_sbn', c_int, [_P, POINTER(CdSbnArgs), _P]),
+    ('ptta_op_cd_densify', c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    ('ptta_op_cd_dense', c_int, [c_int, _P, _P, _P, _P, POINTER(c_int), POINTER(c_float), _P]),
     ('ptta_version', c_int, []),
 ]
 
@@ -169,4 +186,4 @@ def ptr(t):
     return c_void_p(t.data_ptr())
 
 
-__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'SIGNATURES', 'LIB_PATH', 'byref']
+__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'SIGNATURES', 'LIB_PATH', 'byref']

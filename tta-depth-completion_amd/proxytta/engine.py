@@ -624,3 +624,89 @@ def op_gbn(mode, x, y, st, gamma, beta=None, res=None, g=None, gx=None, gres=Non
     rc = lib.ptta_op_gbn(byref(a), _stream())
     if rc != 0:
         raise RuntimeError('ptta_op_gbn failed (%d)' % rc)
+
+
+class CdSparseSet:
+    """Test hook: the sparse voxel sets of CostDCNet's 3-D encoder (include/ptta.h ptta_cd_sparse) for n frames of h x w pixels, and the
+    sparse kernels that run on them.  Feature tensors are fp32 device tensors [voxels of the level][channels], contiguous."""
+
+    def __init__(self, n, h, w):
+        self.lib = _lib.load()
+        self.h_ = c_void_p()
+        rc = self.lib.ptta_cd_sparse_create(byref(self.h_), n, h, w)
+        if rc != 0:
+            self.h_ = None
+            raise RuntimeError('ptta_cd_sparse_create failed (%d)' % rc)
+        self.n, self.h, self.w = n, h, w
+
+    def close(self):
+        if self.h_:
+            self.lib.ptta_cd_sparse_destroy(self.h_)
+            self.h_ = None
+
+    __del__ = close
+
+    def build(self, sparse, z_step):
+        assert sparse.dtype == torch.float32 and sparse.is_contiguous() and sparse.numel() == self.n * self.h * self.w
+        rc = self.lib.ptta_cd_sparse_build(self.h_, ptr(sparse), float(z_step), _stream())
+        if rc != 0:
+            raise RuntimeError('ptta_cd_sparse_build failed (%d)' % rc)
+
+    def counts(self):
+        cnt = (c_int * 3)()
+        rc = self.lib.ptta_cd_sparse_read(self.h_, 0, cnt, None, 0, None, None, _stream())
+        if rc != 0:
+            raise RuntimeError('ptta_cd_sparse_read failed (%d)' % rc)
+        return [int(v) for v in cnt]
+
+    def read(self, level):
+        """(coords [cnt][4] int32 = (frame, plane, y, x), vol [n][16][h >> level][w >> level] int32, feat_in [cnt] or None) as numpy."""
+        import numpy as np
+        cnt = self.counts()[level]
+        coords = np.zeros((max(cnt, 1), 4), np.int32)
+        vol = np.zeros((self.n, 16, self.h >> level, self.w >> level), np.int32)
+        feat = np.zeros(max(cnt, 1), np.float32) if level == 0 else None
+        rc = self.lib.ptta_cd_sparse_read(self.h_, level, None, coords.ctypes.data_as(c_void_p), max(cnt, 1), vol.ctypes.data_as(c_void_p),
+                                          feat.ctypes.data_as(c_void_p) if feat is not None else None, _stream())
+        if rc != 0:
+            raise RuntimeError('ptta_cd_sparse_read failed (%d)' % rc)
+        return coords[:cnt], vol, (feat[:cnt] if feat is not None else None)
+
+    def conv(self, x, wk, y, lin, lout, ksize, backward=False, acc=False):
+        """forward: x [cnt[lin]][ci] -> y [cnt[lout]][co]; backward: x = dy [cnt[lout]][co] -> y = dx [cnt[lin]][ci] (added when acc)."""
+        k, ci, co = wk.shape
+        assert k == ksize ** 3 and x.shape[1] == (co if backward else ci) and y.shape[1] == (ci if backward else co)
+        rc = self.lib.ptta_op_cd_sparse_conv(self.h_, ptr(x), ptr(wk), ptr(y), lin, lout, ksize, ci, co, int(bool(backward)), int(bool(acc)), _stream())
+        if rc != 0:
+            raise RuntimeError('ptta_op_cd_sparse_conv failed (%d)' % rc)
+
+    def bn(self, mode, level, f, gamma, st, beta=None, res=None, out=None, rm=None, rv=None, nbt=None, repeats=1, relu=False, world=1, y=None, g=None,
+           gx=None, gres=None, acc_res=False, dgamma=None, dbeta=None):
+        a = _lib.CdSbnArgs()
+        a.mode, a.level, a.c, a.relu, a.repeats, a.world, a.acc_res = GBN_MODES[mode], level, int(gamma.numel()), int(bool(relu)), int(repeats), int(world), int(bool(acc_res))
+        for name, t in (('f', f), ('res', res), ('y', y), ('g', g), ('gamma', gamma), ('beta', beta), ('rm', rm), ('rv', rv), ('nbt', nbt), ('out', out),
+                        ('st', st), ('dgamma', dgamma), ('dbeta', dbeta), ('gx', gx), ('gres', gres)):
+            if t is not None:
+                assert t.is_contiguous() and t.dtype == (torch.int64 if name == 'nbt' else torch.float32)
+                setattr(a, name, t.data_ptr())
+        rc = self.lib.ptta_op_cd_sbn(self.h_, byref(a), _stream())
+        if rc != 0:
+            raise RuntimeError('ptta_op_cd_sbn failed (%d)' % rc)
+
+    def densify(self, src, dst, c, backward=False, ldv=0, c0=0):
+        rc = self.lib.ptta_op_cd_densify(self.h_, ptr(src), ptr(dst), int(c), int(bool(backward)), int(ldv), int(c0), _stream())
+        if rc != 0:
+            raise RuntimeError('ptta_op_cd_densify failed (%d)' % rc)
+
+
+def op_cd_dense(op, a, out, dims, b=None, out2=None, fpar=()):
+    """Test hook: one of CostDCNet's dense kernels (include/ptta.h ptta_op_cd_dense; `op` a key of _lib.CD_OPS) on contiguous fp32 device
+    tensors; `dims` / `fpar` as the header lists them per op."""
+    lib = _lib.load()
+    for t in (a, b, out, out2):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    d = (c_int * 12)(*[int(v) for v in dims])
+    f = (ctypes.c_float * 8)(*[float(v) for v in fpar])
+    rc = lib.ptta_op_cd_dense(_lib.CD_OPS[op], ptr(a), ptr(b), ptr(out), ptr(out2), d, f, _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_cd_dense(%s) failed (%d)' % (op, rc))
