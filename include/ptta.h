@@ -48,7 +48,22 @@ typedef void* ptta_stream;              /* hipStream_t */
  * conv 256 -> 48 with bias, BatchNorm2d, + its input), fp32 or PTTA_DTYPE_MIXED.  ptta_adapted_count() is 93: the block's seven tensors
  * first, then every other BatchNorm2d; the reference's list has 97 entries because the block's two BatchNorm2d are listed a second time at
  * its end, and Adam steps them twice per step: ptta_adapted_repeat() is 2 for those four.  Not with PTTA_NLSPN_SYNCBN_ADAPT (-38: that
- * list's repeat structure differs). */
+ * list's repeat structure differs).
+ * PTTA_META_NONE: the network without the meta layer, NLSPNModel_Adapt._forward (nlspnmodel_adapt.py:792-848) -- what loss_type 'pretrain'
+ * and every string without adapt / selfsup / meta / head run (:502-509, :609-616): conv1_rgb feeds fe1 directly, ONE pass per training
+ * forward (no zero-image pass), no heads.  Two handle kinds, fp32 on one rank, both with or without PTTA_NLSPN_LEGACY_OFFSET:
+ *   PTTA_META_NONE alone: the BatchNorm-adaptation baseline, adapt_parameters('meta_bn') on a model whose head was never prepared.
+ *     ptta_adapted_count() is 86 (gamma / beta of every BatchNorm2d: the 'meta_bn' list without conv1_rgb_meta.*, same order),
+ *     ptta_adapted_repeat() 1; batch statistics in train and eval forwards.  ptta_embedding_rows() is 0: ptta_forward_train writes the depth
+ *     only (emb_out / ref_out must be NULL, -22 otherwise); ptta_step, ptta_loss_forward and ptta_loss_backward run with emb = ref = NULL and
+ *     loss_info[3] is exactly 0; ptta_backward takes grad_ref = NULL.  Activations are allocated for n frames, not 2 n.
+ *   PTTA_META_NONE | PTTA_ADAPT_META_ONLY: the source model, the loaded checkpoint before any adaptation.  ptta_adapted_count() is 0;
+ *     ptta_forward_eval normalises every BatchNorm2d with the LOADED running statistics, in the convolution epilogue as on every
+ *     PTTA_ADAPT_META_ONLY handle (option "eval_bn_fused"; a missing buffer: -3 at the first eval forward, naming it).  ptta_forward_train,
+ *     ptta_step, ptta_backward and ptta_adam_step return -38 and leave the handle usable.
+ *   Both: ptta_load_weights accepts and ignores conv1_rgb_meta.*, proj* and pred* keys (a stage-3 checkpoint holds them); ptta_head_*,
+ *     ptta_set_stat_sync, ptta_set_stat_sync_rccl and ptta_set_grad_sync_rccl return -38.  Refused at ptta_create with -38 (reason:
+ *     ptta_last_error(NULL)): another backbone, PTTA_DTYPE_MIXED (no bound measured), PTTA_NLSPN_SYNCBN_ADAPT (no heads to append). */
 /* PTTA_BACKBONE_COSTDCNET: ExternalModel_Adapt(model_name='costdcnet') -- src/costdcnet_model_adapt.py:31-114 ->
  * CostDCNet._rgbd_meta_contrast (external_src/costdcnet/CostDCNet_adapt.py:207-256), res = 16 planes, up_scale = 4
  * (src/costdcnet_model_adapt.py:47-52), adapt_parameters('meta_bn') (:357-378).  meta_mode PTTA_META_1LAYER or PTTA_META_2LAYERS, dtype
@@ -89,7 +104,9 @@ enum { PTTA_DTYPE_F32 = 0, PTTA_DTYPE_MIXED = 1,
        PTTA_MIXED_KEEP_PROXY = 0x100, PTTA_MIXED_KEEP_BACKWARD = 0x200, PTTA_MIXED_KEEP_HEADS = 0x400,
        /* generic engine, comparison only: the data gradients on bf16-ROUNDED weights, one MFMA per product (round 5's mixed mode) */
        PTTA_MIXED_BWD_ROUNDED_W = 0x800 };
-enum { PTTA_META_1LAYER = 0, PTTA_META_2LAYERS = 1 };   /* conv1_rgb_meta = Conv2d(32,32,3) | Res_Conv(32,128) (NLSPN: 48 / 256, CostDCNet: 16 / 64) */
+/* conv1_rgb_meta = Conv2d(32,32,3) | Res_Conv(32,128) (NLSPN: 48 / 256, CostDCNet: 16 / 64) | no meta layer at all (NLSPN only: the source
+ * model and the BatchNorm-adaptation baseline, see PTTA_BACKBONE_NLSPN) */
+enum { PTTA_META_1LAYER = 0, PTTA_META_2LAYERS = 1, PTTA_META_NONE = 2 };
 /* NLSPN only, OR-ed into meta_mode: ExternalModel_Adapt(..., offset=True) -> args.legacy (src/nlspn_model_adapt.py:62):
  * the confidence gathers add each tap's own (dy, dx) to the learned offset (nlspnmodel_adapt.py:297-302).
  * src/tta_main.py:309-317 always constructs the model this way. */
@@ -441,7 +458,7 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  *   "stamps"        0        (diagnostic, 1:) fourteen one-thread nodes of the step's and the prefix's graphs write wall_clock64() ticks since
  *                            the step's first node into the debug tensor "stamps" -- where the branches of a replayed step start and end with
  *                            no profiler attached (tools/step_stamps.py, profiles/r05_step_stamps.txt); results unchanged
- *   "eval_bn_fused" 1        (PTTA_ADAPT_META_ONLY handles only, -38 elsewhere) 0: every BatchNorm2d of the eval forward is its own apply launch
+ *   "eval_bn_fused" 1        (PTTA_ADAPT_META_ONLY handles only, the source model PTTA_META_NONE | PTTA_ADAPT_META_ONLY among them; -38 elsewhere) 0: every BatchNorm2d of the eval forward is its own apply launch
  *                            from the same affine table (1: in the epilogue of the convolution in front of it).  Bit-identical
  *                            (tests/test_gpu_nlspn_meta.py): both forms compute fmaf(conv + bias, scale, shift)
  *   "head_bn_fused" 1        (NLSPN and CostDCNet handles; -38 on MSG_CHN, which has no BatchNorm2d) 0: in the stage-2 head trainer's two

@@ -86,6 +86,7 @@ struct ProgSwap {
 }  // namespace
 
 int GNet::head_build(int reverse) {
+    if (!no_heads_why.empty()) return fail(no_heads_why, -38);
     HeadTrain& h = head;
     if (!h.built) {
         if (stat_sync.world > 1 && h.form != PTTA_HEAD_FORM_SYNCBN) return fail("the plain form of the stage-2 head trainer has no SyncBatchNorm exchange (ptta_head_set_form)", -38);
@@ -139,6 +140,7 @@ int GNet::head_build(int reverse) {
 }
 
 int GNet::head_set_form(int form) {
+    if (!no_heads_why.empty()) return fail(no_heads_why, -38);
     if (form != PTTA_HEAD_FORM_PLAIN && form != PTTA_HEAD_FORM_SYNCBN) return fail("ptta_head_set_form: PTTA_HEAD_FORM_PLAIN or PTTA_HEAD_FORM_SYNCBN", -22);
     if (head.stepped) return fail("ptta_head_set_form: the form is chosen before the first head step", -3);
     if (form == PTTA_HEAD_FORM_SYNCBN && mixed) return fail("the SyncBatchNorm form of the stage-2 head trainer needs an fp32 handle", -38);
@@ -147,6 +149,7 @@ int GNet::head_set_form(int form) {
 }
 
 int GNet::head_bind(const char* name_, float* p, float* m, float* v) {
+    if (!no_heads_why.empty()) return fail(no_heads_why, -38);
     if (!name_ || !p) return fail("ptta_head_bind: missing argument", -22);
     NRUN(head_build(-1));
     HeadTrain& h = head;
@@ -163,6 +166,7 @@ int GNet::head_bind(const char* name_, float* p, float* m, float* v) {
 }
 
 int GNet::head_set_hparams(float lr, float b1, float b2, float eps, float wd, float tau, int adam_step, hipStream_t s) {
+    if (!no_heads_why.empty()) return fail(no_heads_why, -38);
     NRUN(head_build(-1));
     const float hy[5] = {lr, b1, b2, eps, wd};
     const float t2[2] = {tau, (float)(1.0 - (double)tau)};
@@ -195,12 +199,14 @@ int GNet::head_sync_packed(bool targets_too, hipStream_t s) {
 }
 
 int GNet::head_reload(hipStream_t s) {
+    if (!no_heads_why.empty()) return fail(no_heads_why, -38);
     NRUN(head_build(-1));
     drop_graphs();
     return head_sync_packed(true, s);
 }
 
 int GNet::head_forward(const float* image, const float* sparse, int reverse, float* emb_out, float* ref_out, hipStream_t s) {
+    if (!no_heads_why.empty()) return fail(no_heads_why, -38);
     if (stat_sync.world > 1 && head.form != PTTA_HEAD_FORM_SYNCBN) return fail("the plain form of the stage-2 head trainer has no SyncBatchNorm exchange (ptta_head_set_form)", -38);
     NRUN(head_build(reverse ? 1 : 0));
     HeadTrain& h = head;
@@ -260,6 +266,7 @@ int GNet::head_forward(const float* image, const float* sparse, int reverse, flo
 }
 
 int GNet::head_backward(float* loss_out, hipStream_t s) {
+    if (!no_heads_why.empty()) return fail(no_heads_why, -38);
     HeadTrain& h = head;
     if (!h.built || !h.fwd_ok) return fail("ptta_head_backward needs the activations of the last ptta_head_forward", -3);
     if (ptta_launch_prepare_loss(T[h.t_emb].p, T[h.t_ref].p, rows(), h.spec.out, T[h.t_emb].g, h.loss_part, h.loss, s)) return fail("prepare loss failed", -5);
@@ -274,6 +281,7 @@ int GNet::head_backward(float* loss_out, hipStream_t s) {
 }
 
 int GNet::head_adam_step(hipStream_t s) {
+    if (!no_heads_why.empty()) return fail(no_heads_why, -38);
     HeadTrain& h = head;
     if (!h.built || !h.bwd_ok) return fail("ptta_head_adam_step needs the gradients of ptta_head_backward", -3);
     if (h.adam_dirty) {
@@ -297,6 +305,7 @@ int GNet::head_adam_step(hipStream_t s) {
 }
 
 int GNet::head_get_grad(const char* name, float* dst, int64_t capacity, int* has_grad_host, hipStream_t s) {
+    if (!no_heads_why.empty()) return fail(no_heads_why, -38);
     HeadTrain& h = head;
     if (!h.built) return fail("no head parameter bound", -3);
     auto it = h.aid.find(name ? name : "");

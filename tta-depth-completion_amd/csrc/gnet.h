@@ -208,6 +208,13 @@ struct GNet {
     // per-channel affine (Op::st_eval, built once per load by prepare_eval_affines) that runs in the producing convolution's epilogue
     // (eval_bn_fused, option "eval_bn_fused") or as a separate gbn_apply; no statistics pass either way
     int meta_only = 0, eval_bn_fused = 1;
+    // one-pass training mode (include/ptta.h PTTA_META_NONE; the reference's `_forward`, nlspnmodel_adapt.py:792-848): a training forward is ONE
+    // pass over the caller's frames -- no zero-image proxy pass, no heads.  A W_BOTH view holds `per` images in train mode too, BatchNorm and
+    // the convolution epilogue's partial sums run one pass, the program holds no W_PROXY op and its tensors are allocated for `per` items.
+    int one_pass = 0;
+    int passes(int which, bool train) const { return (which == gnet::W_BOTH && train && !one_pass) ? 2 : 1; }
+    // why a handle without heads / without an adapted list refuses an entry point (-38); empty: it does not
+    std::string no_heads_why, no_train_why, one_rank_why;
     void plan_eval_affine() { plan_affine((int)ops.size(), false); }
     int prepare_eval_affines(hipStream_t s);
     void plan_affine(int end, bool stage2);
@@ -328,7 +335,7 @@ struct GNet {
     GView view(int t, int which, bool train, bool grad = false) const {
         const Tn& tn = T[t];
         GView v; v.H = tn.H; v.W = tn.W; v.C = tn.C; v.ld = tn.ld;
-        v.B = (which == gnet::W_BOTH && train) ? 2 * tn.per : tn.per;
+        v.B = passes(which, train) * tn.per;
         v.p = (grad ? tn.g : tn.p);
         if (which == gnet::W_PROXY && !grad) v.p += (size_t)tn.per * tn.H * tn.W * tn.ld;
         return v;
@@ -533,5 +540,6 @@ struct GNet {
                       int64_t rows_, float* grad_depth_out, float* grad_ref_out, hipStream_t s);
     int backward_from(const float* grad_depth, const float* grad_ref, hipStream_t s);
     int adam_step(hipStream_t s);
+    int adam_step_checked(hipStream_t s) { return no_train_why.empty() ? adam_step(s) : fail("ptta_adam_step: " + no_train_why, -38); }
     int upload_adam_table(hipStream_t s);
 };

@@ -162,9 +162,9 @@ int GNet::run_conv_fwd(const Op& o, bool train, hipStream_t s, const Op* aff) {
         a.nchunks = (a.C0 + 31) / 32 + (a.C1 + 31) / 32; a.nf0 = 0; a.nnf = (cw.Co + 31) / 32;
         a.y = y.p; a.ldy = y.ld; a.Cy = y.C; a.bias = bias; a.act = o.act; a.vert = cw.vcol;
         if (cw.ff_l2 && o.yw != W_PROXY && x6_layer(o.wname)) {               // bf16x6 for the real frames (they come first in a [real | proxy] batch)
-            a.wl2 = (const uint4*)cw.ff_l2; a.six_B = (o.yw == W_BOTH && train) ? y.B / 2 : y.B;
+            a.wl2 = (const uint4*)cw.ff_l2; a.six_B = passes(o.yw, train) == 2 ? y.B / 2 : y.B;
         }
-        if ((mixed & 1) && train && o.yw != W_GRAD) a.x1_from_B = o.yw == W_BOTH ? y.B / 2 : 0;     // the proxy frames' products: one MFMA
+        if ((mixed & 1) && train && o.yw != W_GRAD && !one_pass) a.x1_from_B = o.yw == W_BOTH ? y.B / 2 : 0;     // the proxy frames' products: one MFMA
         if (aff) {          // y = act(fmaf(conv + bias, scale, shift) [+ res]): the BN's activation, or the BasicBlock's ReLU behind the sum
             a.scale = aff->st_eval + 2 * y.C; a.shift = aff->st_eval + 3 * y.C;
             a.act = aff->res >= 0 ? GACT_RELU : aff->act;
@@ -173,7 +173,7 @@ int GNet::run_conv_fwd(const Op& o, bool train, hipStream_t s, const Op* aff) {
             if (aff->res >= 0) { const GView r = view(aff->res, aff->xw[0], train); a.res = r.p; a.ld_res = r.ld; }
         }
         if (o.stat_to >= 0 && !(meta_only && !train) && (train || !ops[o.stat_to].tracked) && !(bn_prepare && !ops[o.stat_to].tracked) && !bn_eval_in_train(ops[o.stat_to])) {
-            a.stat_part = ops[o.stat_to].part; a.stat_C = y.C; a.stat_npass = (o.yw == W_BOTH && train) ? 2 : 1;
+            a.stat_part = ops[o.stat_to].part; a.stat_C = y.C; a.stat_npass = passes(o.yw, train);
         }
         int rc;
         if (o.stride == 1 && !o.transposed) rc = ptta_launch_gconv_x3(a, o.k, s);
@@ -198,7 +198,7 @@ int GNet::run_conv_fwd(const Op& o, bool train, hipStream_t s, const Op* aff) {
 int GNet::run_bn_fwd(const Op& o, bool train, hipStream_t s) {
     GView x = view(o.x[0], o.xw[0], train), y = view(o.y, o.yw, train);
     GView res; if (o.res >= 0) res = view(o.res, o.xw[0], train);
-    const int npass = (o.xw[0] == W_BOTH && train) ? 2 : 1;
+    const int npass = passes(o.xw[0], train);
     if (meta_only && !train && !o.tracked && !bn_prepare) { // meta-only mode, eval forward: the constant affine of the loaded running statistics
         if (!o.st_eval_valid) return fail("eval affine of " + o.bname + " not prepared", -3);
         if (eval_bn_fused && o.aff_from >= 0) return run_conv_fwd(ops[o.aff_from], false, s, &o);
@@ -301,7 +301,7 @@ int GNet::run_bn_bwd(const Op& o, hipStream_t s) {
     const GView x = view(o.x[0], W_GRAD, true), y = view(o.y, W_GRAD, true);
     const GView g = view(o.y, W_GRAD, true, true), gx = view(o.x[0], W_GRAD, true, true);
     GView gres; if (o.res >= 0) gres = view(o.res, W_GRAD, true, true);
-    const int npass = o.xw[0] == W_BOTH ? 2 : 1;
+    const int npass = passes(o.xw[0], true);
     float* dg = o.ad_g >= 0 ? gall + adapted[o.ad_g].goff : nullptr;
     float* db = o.ad_beta >= 0 ? gall + adapted[o.ad_beta].goff : nullptr;
     if (ptta_launch_gbn_backward(x, g, y, gx, gres, npass, o.act, (o.res >= 0 && o.res_relu) ? 1 : 0, o.first_raw ? 0 : 1, o.first_res ? 0 : 1,
@@ -330,6 +330,8 @@ int GNet::bind_adapted(const char* name, float* p, float* m, float* v) {
     return 0;
 }
 int GNet::forward_train(const float* image, const float* sparse, float* depth_out, float* emb, float* ref, hipStream_t s) {
+    if (!no_train_why.empty()) return fail("ptta_forward_train: " + no_train_why, -38);
+    if ((emb && t_emb < 0) || (ref && t_ref < 0)) return fail("ptta_forward_train: this handle has no heads, emb_out / ref_out must be NULL (PTTA_META_NONE)", -22);
     const int rc = forward(image, sparse, true, s);
     if (rc) return rc;
     const size_t nb_ = (size_t)Nu * Hu * Wu * sizeof(float), eb = (size_t)rows() * emb_dim() * sizeof(float);
@@ -399,6 +401,7 @@ int GNet::adam_step(hipStream_t s) {
     return 0;
 }
 int GNet::step(const float* image, const float* loss_image, const float* sparse, const float* validity, float* depth_out, float* loss_info_out, hipStream_t s) {
+    if (!no_train_why.empty()) return fail("ptta_step: " + no_train_why, -38);
     for (auto& ad : adapted) if (!ad.p || !ad.m || !ad.v) return fail("Adam state of " + ad.name + " not bound", -3);
     if (!loss_image) loss_image = image;
     int rc;
@@ -422,12 +425,13 @@ int GNet::step(const float* image, const float* loss_image, const float* sparse,
 int GNet::step_body(const float* image, const float* loss_image, const float* sparse, const float* validity, hipStream_t s) {
     int rc = forward(image, sparse, true, s);
     if (rc) return rc;
-    const float* emb = T[t_emb].p; const float* ref = T[t_ref].p;
+    // a handle without heads (one_pass): no cosine term -- loss_info[3] is exactly 0, the loss gradient reaches the depth alone
+    const float* emb = t_emb >= 0 ? T[t_emb].p : nullptr; const float* ref = t_ref >= 0 ? T[t_ref].p : nullptr;
     // validity == NULL: evaluated inside the loss kernels; the finalisation runs inside the two gradient kernels
     if (ptta_launch_loss_forward(depth, loss_image, sparse, validity, hp.max_input_depth, emb, ref, rows(), emb_dim(), hyper + 5,
                                  Nu, Hu, Wu, loss_ws, loss_info, s, 1)) return fail("loss forward failed", -5);
     if (ptta_launch_loss_backward(depth, loss_image, sparse, validity, hp.max_input_depth, emb, ref, rows(), emb_dim(), Nu, Hu,
-                                  Wu, loss_ws, gdepth, T[t_ref].g, s, hyper + 5, loss_info)) return fail("loss backward failed", -5);
+                                  Wu, loss_ws, gdepth, t_ref >= 0 ? T[t_ref].g : nullptr, s, hyper + 5, loss_info)) return fail("loss backward failed", -5);
     rc = backward(s);
     if (rc) return rc;
     if (grad_comm && ptta_rccl_allreduce_mean_f32(grad_comm, gall, gall_n, (ptta_stream)s)) return fail(std::string("gradient all-reduce: ") + ptta_rccl_last_error(), -5);
@@ -501,10 +505,13 @@ int GNet::loss_backward(const float* loss_image, const float* depth_, const floa
     return 0;
 }
 int GNet::backward_from(const float* grad_depth, const float* grad_ref, hipStream_t s) {
+    if (!no_train_why.empty()) return fail("ptta_backward: " + no_train_why, -38);
+    if (grad_ref && t_ref < 0) return fail("ptta_backward: this handle has no heads, grad_ref must be NULL (PTTA_META_NONE)", -22);
     if (!fwd_valid) return fail("ptta_backward without a preceding ptta_forward_train", -3);
     const size_t nb_ = (size_t)Nu * Hu * Wu * sizeof(float), rb = (size_t)rows() * emb_dim() * sizeof(float);
     if (hipMemcpyAsync(gdepth, grad_depth, nb_, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail("memcpy failed", -5);
-    if (grad_ref) { if (hipMemcpyAsync(T[t_ref].g, grad_ref, rb, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail("memcpy failed", -5); }
+    if (t_ref < 0) {}
+    else if (grad_ref) { if (hipMemcpyAsync(T[t_ref].g, grad_ref, rb, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail("memcpy failed", -5); }
     else if (hipMemsetAsync(T[t_ref].g, 0, rb, s) != hipSuccess) return fail("memset failed", -5);
     return backward(s);
 }

@@ -7,6 +7,10 @@
 // meta-only (PTTA_ADAPT_META_ONLY; adapt_parameters('meta') / ('meta_fix'), src/nlspn_model_adapt.py:302-320): conv1_rgb_meta's weight and bias
 // alone adapt; every BatchNorm2d keeps its loaded gamma / beta and its running statistics (track_running_stats = False: batch statistics in
 // train mode, no buffer written; the loaded running statistics in the scored eval forward, src/tta_main.py:729-736) -- gnet.h GNet::meta_only.
+// no meta layer (PTTA_META_NONE; `_forward`, nlspnmodel_adapt.py:792-848, what loss_type 'pretrain' and every string without adapt / selfsup /
+// meta / head run): conv1_rgb feeds fe1 directly, one pass per training forward (gnet.h GNet::one_pass), no heads.  Alone it is the
+// BatchNorm-adaptation baseline (adapt_parameters('meta_bn') on a model whose head was never prepared: gamma / beta of every BatchNorm2d, 86
+// tensors, batch statistics in train and eval mode); with PTTA_ADAPT_META_ONLY it is the source model (nothing adapts, eval forward only).
 //
 // The network is a flat op list built once per handle ("program"): CONV (one or two channel-concatenated
 // sources, so torch.cat never materialises), BN (+activation, + residual add of a BasicBlock), then the fused
@@ -69,23 +73,24 @@ struct nlspn_engine : GNet {
     int t_sd16 = -1;
     int t_img = -1, t_sd = -1, t_pred = -1, t_oa = -1, t_conf = -1, t_fe6 = -1;
     float *off9 = nullptr, *aff9 = nullptr, *goff9 = nullptr, *gaff9 = nullptr, *feats = nullptr, *gy = nullptr, *gping = nullptr;
-    int legacy = 0, heads_adapted = 0, meta2 = 0;
+    int legacy = 0, heads_adapted = 0, meta2 = 0, nometa = 0;
     bool fz = false;                   // meta-only mode: every BatchNorm2d frozen (gamma / beta loaded, not adapted)
     int enc_ops_end = 0;               // ops [0, enc_ops_end) = conv1 .. conv6: what the stage-2 head trainer runs of the backbone
 
     static int half(int v) { return (v + 1) / 2; }                 // 3x3 stride 2 padding 1: ceil
-    long rows() const override { return (long)N * half(half(half(half(H)))) * half(half(half(half(W)))); }
+    long rows() const override { return nometa ? 0 : (long)N * half(half(half(half(H)))) * half(half(half(half(W)))); }
     int emb_dim() const override { return 1024; }
 
     void build() {
         // encoder sizes: every stride-2 3x3 convolution (padding 1) halves with ceil; fe2 is at full resolution (layer1 has
         // stride 1), fe3 1/2, fe4 1/4, fe5 1/8, fe6 1/16
         const int H2 = half(H), W2 = half(W), H4 = half(H2), W4 = half(W2), H8 = half(H4), W8 = half(W4), H16 = half(H8), W16 = half(W8);
-        const int N2 = 2 * N;
+        const int N2 = one_pass ? N : 2 * N;         // no meta layer: one pass, tensors for N frames
         // the adapted meta conv comes first in the reference's parameter list (src/nlspn_model_adapt.py:324-328)
         const std::string MP = "conv1_rgb_meta.conv1_meta";
         int ad_mw = -1, ad_mb = -1, ad_w1 = -1;
-        if (!meta2) {
+        if (nometa) {
+        } else if (!meta2) {
             ad_mw = add_adapted("conv1_rgb_meta.weight", 48L * 48 * 9); ad_mb = add_adapted("conv1_rgb_meta.bias", 48);
         } else {
             // Res_Conv's seven parameters in named_parameters order; the BatchNorm pass (:329-337) lists its two BatchNorm2d again after
@@ -101,11 +106,13 @@ struct nlspn_engine : GNet {
         t_img = tensor("image", N2, H, W, naive ? 3 : 16, false);
         t_sd = tensor("sparse", N2, H, W, 1, false);
         const int sd16 = naive ? t_sd : tensor("sparse16", N2, H, W, 16, false);
-        const int rgb1 = tensor("rgb1", N2, H, W, 48, false);
+        const int rgb1 = nometa ? -1 : tensor("rgb1", N2, H, W, 48, false);
         const int fe1 = tensor("fe1", N2, H, W, 64, true);
         const int fe1_rgb = slice("fe1_rgb", fe1, 0, 48), fe1_dep = slice("fe1_dep", fe1, 48, 16);
-        conv("conv1_rgb.0", t_img, -1, rgb1, 3, 1, 0, GACT_LRELU, W_BOTH, W_BOTH, false, false);
-        if (!meta2) {
+        // without the meta layer conv1_rgb writes its slice of fe1 itself (pixel stride 64), as conv1_dep does
+        conv("conv1_rgb.0", t_img, -1, nometa ? fe1_rgb : rgb1, 3, 1, 0, GACT_LRELU, W_BOTH, W_BOTH, false, false);
+        if (nometa) {
+        } else if (!meta2) {
             conv("conv1_rgb_meta", rgb1, -1, fe1_rgb, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH);
             ops.back().ad_w = ad_mw; ops.back().ad_b = ad_mb;
         } else {
@@ -217,15 +224,18 @@ struct nlspn_engine : GNet {
             return o;
         };
         // module order proj, proj_t, pred (:1340-1342): the order of their BatchNorm parameters in the 94-tensor adapted list
-        const int pz = mlp("proj", fe[6], W_PROXY, 512, 1024, false);
-        t_ref = mlp("proj_t", fe[6], W_GRAD, 512, 1024, true);
-        tid["ref"] = t_ref;
-        t_emb = mlp("pred", pz, W_GRAD, 1024, 1024, false);
-        tid["emb"] = t_emb;
-
-        plan_backward({t_pred, t_oa, t_conf, t_ref});           // written by the propagation / loss gradients
+        if (!nometa) {
+            const int pz = mlp("proj", fe[6], W_PROXY, 512, 1024, false);
+            t_ref = mlp("proj_t", fe[6], W_GRAD, 512, 1024, true);
+            tid["ref"] = t_ref;
+            t_emb = mlp("pred", pz, W_GRAD, 1024, 1024, false);
+            tid["emb"] = t_emb;
+            plan_backward({t_pred, t_oa, t_conf, t_ref});       // written by the propagation / loss gradients
+        } else {
+            plan_backward({t_pred, t_oa, t_conf});              // `_forward` has no heads: the loss gradient reaches the depth alone
+        }
         if (meta_only) plan_eval_affine();
-        plan_head_affine(enc_ops_end);                         // stage-2 head trainer: conv1 .. conv6 (head_features)
+        if (!nometa) plan_head_affine(enc_ops_end);            // stage-2 head trainer: conv1 .. conv6 (head_features)
         // ---- remaining workspace ----
         const long P = (long)H * W;
         off9 = falloc((size_t)N * P * 18); aff9 = falloc((size_t)N * P * 9);
@@ -233,12 +243,15 @@ struct nlspn_engine : GNet {
         feats = falloc((size_t)(PROP_TIME + 1) * N * P);
         gy = falloc((size_t)N * P); gping = falloc((size_t)N * P);
         S = falloc(1);
-        alloc_common((long)N * P, 48, meta2 ? 256 : 48);        // weight-gradient partials of the widest adapted conv (48 <-> 256 under 2layers)
+        if (nometa) alloc_common(1, 16, 16);                    // no convolution has a weight gradient: the smallest partial buffer
+        else alloc_common((long)N * P, 48, meta2 ? 256 : 48);   // weight-gradient partials of the widest adapted conv (48 <-> 256 under 2layers)
     }
 
     // ---- weights that are not convolutions / BatchNorm affine ----------------------------------------------------------
     int load_extra(const std::string& name, const float* src, const int64_t* shape, int ndim, hipStream_t s) override {
         (void)shape; (void)ndim;
+        // a stage-3 checkpoint holds the meta layer and the heads: `_forward` does not run them
+        if (nometa && (name.compare(0, 15, "conv1_rgb_meta.") == 0 || name.compare(0, 4, "proj") == 0 || name.compare(0, 4, "pred") == 0)) return 0;
         auto ends = [&](const char* suf) { const size_t l = strlen(suf); return name.size() >= l && name.compare(name.size() - l, l, suf) == 0; };
         if (ends("num_batches_tracked") || ends("running_mean") || ends("running_var")) {
             const size_t dot = name.rfind('.');
@@ -268,6 +281,7 @@ struct nlspn_engine : GNet {
     int stage_inputs_nhwc(const float* image, const float* sparse, bool train, hipStream_t s);
     // stage-2 head trainer (ghead.hip): rows = fe6 of the real pass / of the zero-image pass (nlspnmodel_adapt.py:1028-1046); MLP(512, 1024, 1024)
     int head_spec(HeadSpec* hs) override {
+        if (nometa) return fail(no_heads_why, -38);
         if (heads_adapted) return fail("the stage-2 head trainer runs on a handle whose heads are not in the adapted list (no PTTA_SYNCBN_ADAPT)", -38);
         hs->x_real = t_fe6; hs->xw_real = W_GRAD; hs->x_proxy = t_fe6; hs->xw_proxy = W_PROXY; hs->hidden = 1024; hs->out = 1024;
         return 0;
@@ -304,7 +318,7 @@ int nlspn_engine::forward(const float* image, const float* sparse, bool train, h
 // inputs: image -> NHWC (normalised on the fly; proxy half = zero image), sparse depth clamped (external_model_adapt.py:108)
 int nlspn_engine::stage_inputs_nhwc(const float* image, const float* sparse, bool train, hipStream_t s) {
     const long P = (long)H * W;
-    const int Be = train ? 2 * N : N;
+    const int Be = (train && !one_pass) ? 2 * N : N;
     GView iv = view(t_img, W_BOTH, train);
     if (ptta_launch_gnchw_to_nhwc(image, N, 3, iv, N, norm_on, norm_div, norm_mean, norm_std, s)) return fail("image staging failed", -5);
     hipLaunchKernelGGL(clamp_dup_kernel, dim3(nb(P * Be)), dim3(256), 0, s, sparse, T[t_sd].p, (long)N * P, Be / N, hp.max_input_depth);
@@ -343,6 +357,12 @@ GNet* nlspn_create(int n, int h, int w, const ptta_hparams* hp, int legacy_offse
     e->N = e->Nu = n; e->H = e->Hu = h; e->W = e->Wu = w; e->hp = *hp; e->legacy = (legacy_offset & 1) ? 1 : 0; e->heads_adapted = (legacy_offset & 2) ? 1 : 0;
     e->meta2 = (legacy_offset & 4) ? 1 : 0;
     e->meta_only = (legacy_offset & 8) ? 1 : 0; e->fz = e->meta_only != 0;
+    e->nometa = (legacy_offset & 16) ? 1 : 0; e->one_pass = e->nometa;
+    if (e->nometa) {
+        e->no_heads_why = "PTTA_META_NONE: this handle runs the network without the meta layer and has no heads (no stage-2 head trainer)";
+        e->one_rank_why = "PTTA_META_NONE: more than one rank is not offered (no statistics or gradient exchange)";
+        if (e->meta_only) e->no_train_why = "the source model (PTTA_META_NONE | PTTA_ADAPT_META_ONLY) adapts nothing: it has the eval forward only";
+    }
     const PttaCreateEnv env = ptta_create_env();
     e->naive = env.naive;          // direct fp32 kernels everywhere (validation)
     e->x6 = 0;                     // (third operand plane: off -- matrix-core bound, parity holds without)

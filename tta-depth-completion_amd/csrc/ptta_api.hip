@@ -46,6 +46,13 @@ int ptta_create(ptta_handle* out, int backbone_id, int meta_mode, int n, int hei
     if (!out) return -1;
     *out = nullptr;
     g_create_err.clear();
+    // no meta layer (include/ptta.h PTTA_META_NONE): NLSPN's `_forward` in fp32 on one rank -- the BatchNorm-adaptation baseline, or with
+    // PTTA_ADAPT_META_ONLY the source model; refused before anything is allocated
+    if ((meta_mode & 0xff) == PTTA_META_NONE) {
+        if (backbone_id != PTTA_BACKBONE_NLSPN) return create_refused("PTTA_META_NONE: the network without the meta layer is built for the NLSPN backbone only");
+        if ((dtype & 0xff) == PTTA_DTYPE_MIXED) return create_refused("PTTA_META_NONE with PTTA_DTYPE_MIXED: no bound has been measured for it");
+        if (meta_mode & PTTA_NLSPN_SYNCBN_ADAPT) return create_refused("PTTA_META_NONE with PTTA_NLSPN_SYNCBN_ADAPT: there are no heads to append to the adapted list");
+    }
     // the meta-only adapted list is built for NLSPN's 1layer meta conv in fp32 (include/ptta.h PTTA_ADAPT_META_ONLY); refused before anything is allocated
     if (meta_mode & PTTA_ADAPT_META_ONLY) {
         if (backbone_id != PTTA_BACKBONE_NLSPN) return create_refused("PTTA_ADAPT_META_ONLY: only the NLSPN adapter has adapt_mode 'meta'");
@@ -64,11 +71,11 @@ int ptta_create(ptta_handle* out, int backbone_id, int meta_mode, int n, int hei
     if (backbone_id == PTTA_BACKBONE_NLSPN) {
         // 2layers: the Res_Conv(48, 256) block (nlspn_api.hip), fp32 and mixed; not with the adapted set of the DDP run (its repeat structure differs)
         const int meta = meta_mode & ~(PTTA_NLSPN_LEGACY_OFFSET | PTTA_NLSPN_SYNCBN_ADAPT | PTTA_ADAPT_META_ONLY);
-        if ((meta != PTTA_META_1LAYER && meta != PTTA_META_2LAYERS) || dtype != PTTA_DTYPE_F32) return -38;
+        if ((meta != PTTA_META_1LAYER && meta != PTTA_META_2LAYERS && meta != PTTA_META_NONE) || dtype != PTTA_DTYPE_F32) return -38;
         if (meta == PTTA_META_2LAYERS && (meta_mode & PTTA_NLSPN_SYNCBN_ADAPT)) return -38;
         int rc = 0;
         GNet* e = nlspn_create(n, height, width, hp, ((meta_mode & PTTA_NLSPN_LEGACY_OFFSET) ? 1 : 0) | ((meta_mode & PTTA_NLSPN_SYNCBN_ADAPT) ? 2 : 0) |
-                               (meta == PTTA_META_2LAYERS ? 4 : 0) | ((meta_mode & PTTA_ADAPT_META_ONLY) ? 8 : 0), &rc);
+                               (meta == PTTA_META_2LAYERS ? 4 : 0) | ((meta_mode & PTTA_ADAPT_META_ONLY) ? 8 : 0) | (meta == PTTA_META_NONE ? 16 : 0), &rc);
         return wrap_gnet(out, e, rc, gmix, n, height, width, hp);
     }
     if (backbone_id == PTTA_BACKBONE_COSTDCNET) {
@@ -340,7 +347,7 @@ int ptta_backward(ptta_handle c, const float* grad_depth, const float* grad_ref,
 }
 
 int ptta_adam_step(ptta_handle c, const float* gw, const float* gb, ptta_stream s_) {
-    if (c && c->nl) return (gw || gb) ? c->fail("explicit gradients are an MSG_CHN 1layer convenience", -22) : c->nl->adam_step((hipStream_t)s_);
+    if (c && c->nl) { c->err.clear(); return (gw || gb) ? c->fail("explicit gradients are an MSG_CHN 1layer convenience", -22) : c->nl->adam_step_checked((hipStream_t)s_); }
 
     if (!c) return -1;
     for (auto& ad : c->adapted) if (!ad.p || !ad.m || !ad.v) return c->fail("Adam state of " + ad.name + " not bound", -3);
@@ -383,6 +390,7 @@ int ptta_set_image_norm(ptta_handle c, float divisor, const float* mean, const f
 // step's stream and are captured like any kernel (RCCL) -- otherwise they are host-driven and the step cannot be replayed.  Either way the
 // second stream is given up while an exchange is on (collectives of one communicator are kept in one stream order).
 static int set_stat_sync(ptta_ctx* c, const PttaStatSync& sy, bool on, bool keeps_graph) {
+    if (c->nl && !c->nl->one_rank_why.empty()) { c->err.clear(); return c->nl->fail(c->nl->one_rank_why, -38); }
     if (c->nl && c->nl->meta_only) { c->err.clear(); return c->nl->fail("the SyncBatchNorm form of the meta-only adaptation mode is not offered (PTTA_ADAPT_META_ONLY)", -38); }
     if (c->nl) { c->err.clear(); c->nl->drop_graphs(); c->nl->stat_sync = sy; return 0; }
     if (on && c->meta_mode == PTTA_META_2LAYERS && !c->m2.generic) return c->fail("SyncBatchNorm needs the default arithmetic for the 2layers meta layer", -38);
@@ -420,6 +428,7 @@ int ptta_set_stat_sync_rccl(ptta_handle c, void* comm, double* exchange_buf, int
 // ncclAllReduce enqueued on the step's stream (captured into the hipGraph).  comm == NULL: off.
 int ptta_set_grad_sync_rccl(ptta_handle c, void* comm) {
     if (!c) return -1;
+    if (c->nl && !c->nl->one_rank_why.empty()) { c->err.clear(); return c->nl->fail(c->nl->one_rank_why, -38); }
     if (c->nl && c->nl->meta_only) { c->err.clear(); return c->nl->fail("no gradient exchange in the meta-only adaptation mode: more than one rank is not offered (PTTA_ADAPT_META_ONLY)", -38); }
     if (c->nl) { c->nl->drop_graphs(); c->nl->grad_comm = comm; return 0; }
     c->grad_comm = comm;

@@ -22,6 +22,7 @@ PTTA_SYNCBN_ADAPT = 0x200
 PTTA_ADAPT_META_ONLY = 0x400
 PTTA_META_1LAYER = 0
 PTTA_META_2LAYERS = 1
+PTTA_META_NONE = 2             # NLSPN without the meta layer: the source model / the BatchNorm-adaptation baseline
 PTTA_DTYPE_F32 = 0
 PTTA_DTYPE_MIXED = 1
 PTTA_HEAD_FORM_PLAIN = 0

@@ -65,6 +65,10 @@ class Engine:
             raise ValueError("adapt_mode must be 'meta_bn', 'meta' or 'meta_fix' (src/nlspn_model_adapt.py:302-337)")
         # 'meta' / 'meta_fix' (NLSPN): the meta conv alone adapts, BatchNorm2d evaluates from its loaded running statistics (include/ptta.h PTTA_ADAPT_META_ONLY)
         self.adapt_mode = adapt_mode
+        # meta 'none' (NLSPN): the network without the meta layer, one pass, no heads (include/ptta.h PTTA_META_NONE) -- with adapt_mode 'meta_bn'
+        # the BatchNorm-adaptation baseline (86 adapted tensors), with 'meta' / 'meta_fix' the source model (nothing adapts, eval forward only)
+        if meta not in ('1layer', '2layers', 'none'):
+            raise ValueError("meta must be '1layer', '2layers' or 'none'")
         self.emb_dim = 1024 if backbone == 'nlspn' else 512
         if backbone == 'costdcnet' and not max_predict_depth:
             raise ValueError('CostDCNet needs max_predict_depth (the far plane of its cost volume, ExternalModel_Adapt(max_predict_depth))')
@@ -81,7 +85,7 @@ class Engine:
             code |= {'proxy': 0x100, 'backward': 0x200, 'heads': 0x400, 'bwd_rounded_w': 0x800}[k]
         rc = self.lib.ptta_create(byref(self.handle),
                                   {'nlspn': _lib.PTTA_BACKBONE_NLSPN, 'costdcnet': _lib.PTTA_BACKBONE_COSTDCNET}.get(backbone, _lib.PTTA_BACKBONE_MSG_CHN),
-                                  (_lib.PTTA_META_2LAYERS if meta == '2layers' else _lib.PTTA_META_1LAYER) |
+                                  {'2layers': _lib.PTTA_META_2LAYERS, 'none': _lib.PTTA_META_NONE}.get(meta, _lib.PTTA_META_1LAYER) |
                                   (_lib.PTTA_NLSPN_LEGACY_OFFSET if (legacy_offset and backbone == 'nlspn') else 0) |
                                   (_lib.PTTA_SYNCBN_ADAPT if (syncbn_adapted and backbone in ('nlspn', 'costdcnet')) else 0) |
                                   (_lib.PTTA_ADAPT_META_ONLY if adapt_mode != 'meta_bn' else 0),
@@ -176,7 +180,7 @@ class Engine:
         sparse = self._f32(sparse, (self.n, 1, self.h, self.w))
         depth = torch.empty((self.n, 1, self.h, self.w), device=image.device, dtype=torch.float32)
         emb = ref = None
-        if want_emb:
+        if want_emb and self.meta != 'none':       # a handle without heads writes the depth only: (depth, None, None)
             emb = torch.empty((self.rows, self.emb_dim), device=image.device, dtype=torch.float32)
             ref = torch.empty_like(emb)
         self._chk(self.lib.ptta_forward_train(self.handle, ptr(image), ptr(sparse), ptr(depth), ptr(emb),
