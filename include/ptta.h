@@ -434,7 +434,7 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  * handle's streams and drops its captured graphs; the next step re-captures.  Every non-default value is a correct, slower form of
  * the same step, kept as the check of the default (tests/test_gpu_options.py) or taken by the library itself where the default
  * form does not apply (small maps, N > 16, SyncBatchNorm exchange).  Unknown key / value out of range: -22; a key the handle does
- * not have: -38 (the generic engine has "graph", "head_bn_fused" and, on PTTA_ADAPT_META_ONLY handles, "eval_bn_fused"; PTTA_DTYPE_MIXED handles keep every key but graph / aux_stream / thru / adam_in_wgrad at 1).
+ * not have: -38 (the generic engine has "graph", "head_bn_fused" and, on PTTA_ADAPT_META_ONLY handles, "eval_bn_fused"; PTTA_DTYPE_MIXED handles keep every key but graph / aux_stream / thru / adam_in_wgrad / pair_fuse at 1).
  *   key             default  meaning of 0
  *   "graph"         0        (1:) ptta_step / ptta_step_pipelined / ptta_forward_eval replay captured hipGraphs from their second call on.  Default
  *                            since round 5: direct launches on the caller's stream and the handle's own streams -- measured FASTER than replay
@@ -455,6 +455,11 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  *   "heads_v2"      1        proj's hidden layer materialised (1: recomputed inside the GEMM from analytic BatchNorm statistics)
  *   "cos_in_gemm"   1        d loss_cos / d ref written as a tensor (1: formed in the backward GEMM's operand staging)
  *   "mask_bits"     1        fp32 pre-activation maps as ReLU masks (1: one word of sign bits per pixel)
+ *   "pair_fuse"     1        every (stride-2 -> stride-1) layer pair as two launches (1: ONE launch where the stride-1 half runs on a small map --
+ *                            at most 256 tiles of 8 x 32 -- and the pair is an instantiated form, csrc/conv_pair.hip: the three encoder pairs of
+ *                            stages 2 and 3 at 1/4 and 1/8 resolution, fp32 and narrow maps, and on PTTA_DTYPE_MIXED handles the three
+ *                            stride-2 pairs of the data gradients).  Bit-identical (tests/test_gpu_conv_pair.py);
+ *                            free on PTTA_DTYPE_MIXED handles
  *   "stamps"        0        (diagnostic, 1:) fourteen one-thread nodes of the step's and the prefix's graphs write wall_clock64() ticks since
  *                            the step's first node into the debug tensor "stamps" -- where the branches of a replayed step start and end with
  *                            no profiler attached (tools/step_stamps.py, profiles/r05_step_stamps.txt); results unchanged
@@ -481,7 +486,9 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  *   "head_bn_fused_count"  how many BatchNorm2d of this handle's stage-2 prefix ride in a convolution epilogue as configured now: 36 (NLSPN),
  *                       38 (NLSPN 2layers), 15 (CostDCNet), 17 (CostDCNet 2layers); 0 with "head_bn_fused" 0, on a PTTA_DTYPE_MIXED handle and with
  *                       PTTA_CONV_IMPL=naive (no matrix-core convolution to ride in); -38 on MSG_CHN
- * bit-identical to the default: aux_stream, thru, adam_in_wgrad, fuse_first, fuse_head_bwd, mask_bits, graph; within bf16x3's own error (documented
+ *   "pair_fuse_count"   how many layer pairs the last step issued as one launch ("pair_fuse"; a replayed graph: as it was captured); 0 with
+ *                       "pair_fuse" 0, on maps too large for the form, with PTTA_CONV_IMPL=naive and PTTA_ARITH=exact
+ * bit-identical to the default: aux_stream, thru, adam_in_wgrad, fuse_first, fuse_head_bwd, mask_bits, graph, pair_fuse; within bf16x3's own error (documented
  * in the tests): fuse_heads, heads_v2, cos_in_gemm.
  * Environment, read once per ptta_create (csrc/ptta_kernels.h ptta_create_env) because it decides allocation and arithmetic:
  *   PTTA_CONV_IMPL=naive (direct fp32 kernels, PTTA_DTYPE_F32 only), PTTA_ARITH=exact (fp32 MFMA, MSG_CHN PTTA_DTYPE_F32 only),
@@ -509,6 +516,20 @@ int ptta_debug_tensor(ptta_handle h, const char* name, float* dst, int64_t capac
 int ptta_op_conv32(const float* in_nhwc, const float* weight, const float* bias, float* out_nhwc,
                    int b, int hin, int win, int mode, int relu_in, int in_major, int flip, int dtype, int naive,
                    ptta_stream s);
+/* Test hook: a (stride-2 | transposed, first_mode 1 | 2) 32->32 convolution followed by a stride-1 one, fp32 NHWC device buffers, as the MSG_CHN
+ * engine issues such a pair: relu1 / relu2 = ReLU on the first / second layer's input; the first layer's ReLU mask as one word of sign bits
+ * per pixel (mask1_bits [b][hm][wm]) and its addend add0 [b][hm][wm][32] -- with add0 the second layer reads the first one's SUM; the second
+ * layer's bilinear x2 skip `up` [b][hm/2][wm/2][32], skip addends add1, add2 (their sum goes to out_sum) and mask words mask2_bits (each
+ * may be NULL); in_nb <= b frames of input (frame b % in_nb); dtype PTTA_DTYPE_F32 (bf16x3) or any other (narrow maps); w2 = the hi + lo
+ * weight form of the narrow data gradients.  fused 1: ONE launch where the pair is an instantiated form on a small map
+ * (csrc/conv_pair.hip), otherwise and with fused 0 two launches; *fused_host = 1 iff the one-launch form ran.  Outputs (NULL: not wanted):
+ * the second layer's map / sum, the first layer's map, sum and (PTTA_DTYPE_F32) sign-bit words.  The two forms are bit-identical.
+ * Synchronises. */
+int ptta_op_conv32_pair(const float* in_nhwc, const float* weight1, const float* bias1, const float* weight2, const float* bias2,
+                        const float* up_nhwc, const float* add0_nhwc, const float* add1_nhwc, const float* add2_nhwc,
+                        const uint32_t* mask1_bits, const uint32_t* mask2_bits, float* out_raw, float* out_sum, float* mid_raw,
+                        float* mid_sum, uint32_t* mid_bits, int b, int in_nb, int hin, int win, int first_mode, int relu1, int relu2,
+                        int in_major, int flip, int dtype, int w2, int fused, int* fused_host, ptta_stream s);
 /* Diagnostic (tests, tools/bench_gwgrad_wide.py): weight and bias gradient of a stride-1 3x3 convolution, dense fp32 NHWC device maps
  * x [b][h][w][ci] and gy [b][h][w][co], 1 <= ci, co <= 256 -> gw [co][ci][3][3], gb [co] (gb may be null).  impl 0: the launcher the engine
  * runs -- bf16x3 on the matrix cores (hi*hi + hi*lo + lo*hi, fp32 accumulation) for Ci, Co <= 64, 32 <-> 128 and, for channel counts that

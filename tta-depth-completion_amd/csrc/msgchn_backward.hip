@@ -150,8 +150,10 @@ int backbone_backward(ptta_ctx* c, const float* g_net, hipStream_t s, bool join_
     CV("depth_decoder3.dec1.1", true, CONV_S2, c->du3, Nn, Nn, H1, W1, false, em(c->ds1_3, c->s1_3, Nn));
     CV("depth_decoder3.dec2.3", true, CONV_S1, c->ds1_3, Nn, Nn, H2, W2, false, em(c->dt3, c->t3, Nn));
     if (join_aux) HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));       // d feat from the heads (auxiliary stream)
+    // (each stride-2 data gradient and the stride-1 one that reads its sum: one launch on small maps, conv32_pair -- here with
+    // depth_encoder3.enc2.3 below, whose ordering against the side upsamplings is unchanged: they read what both halves wrote)
     { E e; e.raw = c->dw2; e.mask = c->w2; e.mask_nb = B2; e.sum = c->dfeat_tot; e.add1 = c->g_feat; e.add1_nb = Nn;
-      CV("depth_decoder3.dec2.1", true, CONV_S2, c->dt3, Nn, Nn, H2, W2, false, e); }
+      RUN(conv32_pair(c, s, true, "depth_decoder3.dec2.1", c->dt3, Nn, Nn, H2, W2, e, "depth_encoder3.enc2.3", Nn, em(c->de3_2a, c->e3_2a, B2))); }
     // The three transposed bilinear upsamplings of the backward (d z2 += up2^T(d feat_tot), d z3 = d s1_2 + up2^T(d e3_1), d z4 = d s0_2 + up2^T(d e3_0))
     // do not lie on the chain d feat_tot -> encoder 3 -> decoder 2: they run on the second stream, and each
     // result enters the chain as the addend of a convolution epilogue (out_sum = masked result + addend; fp32: the same two operands of the
@@ -159,7 +161,6 @@ int backbone_backward(ptta_ctx* c, const float* g_net, hipStream_t s, bool join_
     hipStream_t sd = join_aux ? c->aux(s) : nullptr;
     if (!sd) sd = s;
     // ---- encoder 3 ----
-    CV("depth_encoder3.enc2.3", true, CONV_S1, c->dfeat_tot, Nn, Nn, H4, W4, false, em(c->de3_2a, c->e3_2a, B2));
     { E e; e.sum = c->de3_1; e.mask = c->e3_1; e.mask_nb = B2; e.add1 = c->ds1_3; e.add1_nb = Nn;
       CV("depth_encoder3.enc2.1", true, CONV_T2, c->de3_2a, Nn, Nn, H4, W4, false, e); }
     CV("depth_encoder3.enc1.3", true, CONV_S1, c->de3_1, Nn, Nn, H2, W2, false, em(c->de3_1a, c->e3_1a, B2));
@@ -189,12 +190,10 @@ int backbone_backward(ptta_ctx* c, const float* g_net, hipStream_t s, bool join_
       RUN(head_bwd("depth_decoder2.prdct.3", "depth_decoder2.prdct.1", c->dq, c->v2, c->dv2, H2, W2, e)); }
     CV("depth_decoder2.dec1.3", true, CONV_S1, c->dz4, Nn, Nn, H2, W2, false, em(c->du2, c->u2, B2));
     { E e = em(c->ds1_2, c->s1_2, B2); e.sum = c->dz3; e.add1 = c->up3_t; e.add1_nb = Nn;      // d z3 = d s1_2 + up2^T(d e3_1)
-      CV("depth_decoder2.dec1.1", true, CONV_S2, c->du2, Nn, Nn, H2, W2, false, e); }
-    CV("depth_decoder2.dec2.3", true, CONV_S1, c->dz3, Nn, Nn, H4, W4, false, em(c->dt2, c->t2, B2));
+      RUN(conv32_pair(c, s, true, "depth_decoder2.dec1.1", c->du2, Nn, Nn, H2, W2, e, "depth_decoder2.dec2.3", Nn, em(c->dt2, c->t2, B2))); }
     { E e; e.sum = c->dz2; e.mask = c->z2; e.mask_nb = B2; e.add1 = c->dz2_up; e.add1_nb = Nn;
-      CV("depth_decoder2.dec2.1", true, CONV_S2, c->dt2, Nn, Nn, H4, W4, false, e); }
+      RUN(conv32_pair(c, s, true, "depth_decoder2.dec2.1", c->dt2, Nn, Nn, H4, W4, e, "depth_encoder2.enc2.3", Nn, em(c->de2_2a, c->e2_2a, B2))); }
     // ---- encoder 2 ----
-    CV("depth_encoder2.enc2.3", true, CONV_S1, c->dz2, Nn, Nn, H8, W8, false, em(c->de2_2a, c->e2_2a, B2));
     { E e; e.sum = c->de2_1; e.mask = c->e2_1; e.mask_nb = B2; e.add1 = c->ds1_2; e.add1_nb = Nn;
       CV("depth_encoder2.enc2.1", true, CONV_T2, c->de2_2a, Nn, Nn, H8, W8, false, e); }
     CV("depth_encoder2.enc1.3", true, CONV_S1, c->de2_1, Nn, Nn, H4, W4, false, em(c->de2_1a, c->e2_1a, B2));

@@ -153,6 +153,8 @@ struct ptta_ctx : PrefixBufs {
     hipEvent_t ev_loss = nullptr;
     hipEvent_t ev_dpart = nullptr;
     int fuse_first = 1, fuse_head_bwd = 1;
+    int pair_fuse = 1;               // option "pair_fuse": each small-map stride-2 -> stride-1 layer pair as one launch (conv_pair.hip)
+    int pair_fuse_count = 0;         // fused pair launches issued by the last step (read-only option "pair_fuse_count")
     int cos_grad_fused = 1;          // PTTA_COS_IN_GEMM=0: the fused step writes d loss / d ref as a tensor (loss.hip cos_grad_body) instead
     bool cos_in_gemm = false;        // (set around the fused step's backward only: ptta_backward with a caller's gradient keeps the tensor form)
     void* w0frag = nullptr; float *hm_part = nullptr, *headP = nullptr; double* head_k12 = nullptr;
@@ -348,6 +350,8 @@ int conv_in_p(ptta_ctx* c, const ConvInArgs& a_, hipStream_t s);
 int conv_out1_p(ptta_ctx* c, const ConvOut1Args& a, hipStream_t s);
 int conv32(ptta_ctx* c, hipStream_t s, const std::string& layer, bool bwd, int mode, const void* in, int in_nb,
            int B, int Hin, int Win, bool relu, const E& e);
+int conv32_pair(ptta_ctx* c, hipStream_t s, bool bwd, const std::string& first, const void* in, int in_nb, int B, int Hin, int Win, const E& fe,
+                const std::string& second, int mid_nb, const E& se);
 int conv32w(ptta_ctx* c, hipStream_t s, const ConvW* w, const float* bias, const void* in, int in_nb, int B, int H, int W, const E& e);
 int conv32_first_bwd(ptta_ctx* c, hipStream_t s, const std::string& layer, ConvInArgs& f, int B, int H, int W, const E& e);
 int to_narrow(ptta_ctx* c, const void* src_f32, void* dst, long n, hipStream_t s);

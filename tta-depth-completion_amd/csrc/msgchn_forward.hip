@@ -34,18 +34,17 @@ int conv_out1_p(ptta_ctx* c, const ConvOut1Args& a, hipStream_t s) {
     return ptta_launch_conv_out1(a, s);
 }
 
-int conv32(ptta_ctx* c, hipStream_t s, const std::string& layer, bool bwd, int mode, const void* in, int in_nb,
-           int B, int Hin, int Win, bool relu, const E& e) {
+// the launch arguments of one 32 -> 32 layer as conv32() issues it
+static int conv32_args(ptta_ctx* c, Conv32Args& a, const std::string& layer, bool bwd, int mode, const void* in, int in_nb,
+                       int B, int Hin, int Win, bool relu, const E& e) {
     auto it = c->l32.find(layer);
     if (it == c->l32.end()) return c->fail("unknown 32->32 layer " + layer, -2);
-    Conv32Args a;
     a.in = in; a.in_nb = in_nb; a.w = bwd ? &it->second.b : &it->second.f;
     a.bias = bwd ? nullptr : (layer == "conv1_rgb_meta" ? c->meta_b : it->second.bias);
     a.up = e.up; a.up_nb = e.up_nb; a.mask = e.mask; a.mask_nb = e.mask_nb;
     a.add1 = e.add1; a.add1_nb = e.add1_nb; a.add2 = e.add2; a.add2_nb = e.add2_nb;
     a.out_raw = e.raw; a.out_sum = e.sum;
     const bool nar = e.nar || (bwd && c->nar_bwd);
-    const int es_l = nar ? 2 : c->es;
     a.B = B; a.Hin = Hin; a.Win = Win; a.mode = mode; a.relu_in = relu ? 1 : 0; a.bf16 = nar ? 1 : c->bf16; a.naive = c->naive; a.x3 = c->x3;
     a.w2 = (bwd && c->nar_bwd && c->bwd_w2) ? 1 : 0;
     if (!c->mbits.empty()) {
@@ -58,6 +57,24 @@ int conv32(ptta_ctx* c, hipStream_t s, const std::string& layer, bool bwd, int m
             if (bs || br) { a.bits_out = bs ? bs : br; a.bits_sum = bs ? 1 : 0; a.bits_nb = c->Nn; }
         }
     }
+    return 0;
+}
+
+// algorithmic bytes and MACs of one 32 -> 32 launch (SURVEY.md 8d counting rule): input + output + weight elements x element size,
+// output pixels x 9 x 32 x 32
+static void conv32_cost(int mode, int B, int Hin, int Win, int es_l, double& bytes, double& macs) {
+    const long pin = (long)B * Hin * Win;
+    const long pout = mode == CONV_S1 ? pin : (mode == CONV_S2 ? pin / 4 : pin * 4);
+    bytes = (double)((pin + pout) * 32 + 9216) * es_l;
+    macs = (double)(mode == CONV_T2 ? pin : pout) * 9.0 * 32.0 * 32.0;
+}
+
+int conv32(ptta_ctx* c, hipStream_t s, const std::string& layer, bool bwd, int mode, const void* in, int in_nb,
+           int B, int Hin, int Win, bool relu, const E& e) {
+    Conv32Args a;
+    { const int rc = conv32_args(c, a, layer, bwd, mode, in, in_nb, B, Hin, Win, relu, e); if (rc) return rc; }
+    const bool nar = e.nar || (bwd && c->nar_bwd);
+    const int es_l = nar ? 2 : c->es;
     // profiling leg (bench.py roofline): bracket this launch with events on ITS stream; algorithmic bytes = input + output + weight
     // elements x element size, MACs = output pixels x 9 x 32 x 32 (SURVEY.md 8d counting rule)
     const long pin = (long)B * Hin * Win;
@@ -71,6 +88,36 @@ int conv32(ptta_ctx* c, hipStream_t s, const std::string& layer, bool bwd, int m
     ProfScope ps(c, (mode == CONV_S1 ? (relu ? 0 : 2) : 4) + (small ? 1 : 0), s, (double)((pin + pout) * 32 + 9216) * es_l,
                  (double)(mode == CONV_T2 ? pin : pout) * 9.0 * 32.0 * 32.0, 1);
     return ptta_launch_conv32(a, s);
+}
+
+// A stride-2 layer and the stride-1 layer that consumes its output (`fe.sum` when the first layer has one, else `fe.raw`; both stay side
+// outputs), forward (ReLU on both inputs) or data gradients (bwd, no ReLU): ONE launch where the stride-1
+// half would take the small-map kernel, the arithmetic is the default one, option "pair_fuse" is on and the pair's epilogue combination is
+// instantiated (conv_pair.hip); otherwise exactly the two conv32() calls.
+int conv32_pair(ptta_ctx* c, hipStream_t s, bool bwd, const std::string& first, const void* in, int in_nb, int B, int Hin, int Win, const E& fe,
+                const std::string& second, int mid_nb, const E& se) {
+    const int Hm = Hin / 2, Wm = Win / 2;
+    const bool relu = !bwd;
+    void* const mid = fe.sum ? fe.sum : fe.raw;
+    const bool nar = fe.nar || (bwd && c->nar_bwd);
+    if (c->pair_fuse && !c->naive && (c->x3 || c->bf16 || nar) && fe.nar == se.nar && mid) {
+        Conv32Args f, g;
+        { const int rc = conv32_args(c, f, first, bwd, CONV_S2, in, in_nb, B, Hin, Win, relu, fe); if (rc) return rc; }
+        { const int rc = conv32_args(c, g, second, bwd, CONV_S1, mid, mid_nb, B, Hm, Wm, relu, se); if (rc) return rc; }
+        if (mid_nb == B && ptta_conv32_pair_applies(f, g)) {
+            const int es_l = nar ? 2 : c->es;
+            double b1, m1, b2, m2;
+            conv32_cost(CONV_S2, B, Hin, Win, es_l, b1, m1); conv32_cost(CONV_S1, B, Hm, Wm, es_l, b2, m2);
+            // (both layers' algorithmic bytes and MACs as counted for the two launches: the launch executes both)
+            ProfScope ps(c, 5, s, b1 + b2, m1 + m2, 1);
+            const int rc = ptta_launch_conv32_pair(f, g, s);
+            if (rc == 1) return c->fail("conv32_pair: fused form refused a case its own test accepted", -22);
+            if (rc == 0) c->pair_fuse_count++;
+            return rc;
+        }
+    }
+    { const int rc = conv32(c, s, first, bwd, CONV_S2, in, in_nb, B, Hin, Win, relu, fe); if (rc) return rc; }
+    return conv32(c, s, second, bwd, CONV_S1, mid, mid_nb, B, Hm, Wm, relu, se);
 }
 
 int conv32w(ptta_ctx* c, hipStream_t s, const ConvW* w, const float* bias, const void* in, int in_nb, int B, int H, int W, const E& e) {
@@ -407,11 +454,11 @@ static int backbone(ptta_ctx* c, const float* image, bool train, hipStream_t s) 
             E e; e.nar = nar; e.raw = A(c->e2_0, H2, W2); e.up = A(c->y4, H4, W4); e.up_nb = Bl;
             RUN(conv32_first(c, st, "depth_encoder2.init.2", a, (b0 == 0 && !nar) ? Nn : 0, Bl, H2, W2, e));
         }
-        CR("depth_encoder2.enc1.1", false, CONV_S2, A(c->e2_0, H2, W2), Bl, Bl, H2, W2, true, raw(A(c->e2_1a, H4, W4)));
-        { E e; e.nar = nar; e.raw = A(c->e2_1, H4, W4); e.up = A(c->y3, H8, W8); e.up_nb = Bl; CR("depth_encoder2.enc1.3", false, CONV_S1, A(c->e2_1a, H4, W4), Bl, Bl, H4, W4, true, e); }
-        CR("depth_encoder2.enc2.1", false, CONV_S2, A(c->e2_1, H4, W4), Bl, Bl, H4, W4, true, raw(A(c->e2_2a, H8, W8)));
+        // (each stride-2 layer and the stride-1 layer behind it: one launch on small maps, conv32_pair)
+        { E e; e.nar = nar; e.raw = A(c->e2_1, H4, W4); e.up = A(c->y3, H8, W8); e.up_nb = Bl;
+          RUN(conv32_pair(c, st, false, "depth_encoder2.enc1.1", A(c->e2_0, H2, W2), Bl, Bl, H2, W2, raw(A(c->e2_1a, H4, W4)), "depth_encoder2.enc1.3", Bl, e)); }
         { E e; e.nar = nar; e.sum = A(c->z2, H8, W8); e.up = A(c->y2, H16, W16); e.up_nb = Bl; e.add1 = A(c->c3, H8, W8); e.add1_nb = Bl;            // z2 = e2_2 + c3
-          CR("depth_encoder2.enc2.3", false, CONV_S1, A(c->e2_2a, H8, W8), Bl, Bl, H8, W8, true, e); }
+          RUN(conv32_pair(c, st, false, "depth_encoder2.enc2.1", A(c->e2_1, H4, W4), Bl, Bl, H4, W4, raw(A(c->e2_2a, H8, W8)), "depth_encoder2.enc2.3", Bl, e)); }
         CR("depth_decoder2.dec2.1", false, CONV_T2, A(c->z2, H8, W8), Bl, Bl, H8, W8, true, raw(A(c->t2, H4, W4)));
         { E e; e.nar = nar; e.raw = A(c->z3, H4, W4); e.sum = A(c->s1_2, H4, W4); e.add1 = A(c->e2_1, H4, W4); e.add1_nb = Bl; e.add2 = A(c->m, H4, W4); e.add2_nb = Bl;
           CR("depth_decoder2.dec2.3", false, CONV_S1, A(c->t2, H4, W4), Bl, Bl, H4, W4, true, e); }
@@ -439,10 +486,9 @@ static int backbone(ptta_ctx* c, const float* image, bool train, hipStream_t s) 
         }
         CR("depth_encoder3.enc1.1", false, CONV_S2, A(c->e3_0, H1, W1), Bl, Bl, H1, W1, true, raw(A(c->e3_1a, H2, W2)));
         { E e; e.nar = nar; e.raw = A(c->e3_1, H2, W2); e.up = A(c->z3, H4, W4); e.up_nb = Bl; CR("depth_encoder3.enc1.3", false, CONV_S1, A(c->e3_1a, H2, W2), Bl, Bl, H2, W2, true, e); }
-        CR("depth_encoder3.enc2.1", false, CONV_S2, A(c->e3_1, H2, W2), Bl, Bl, H2, W2, true, raw(A(c->e3_2a, H4, W4)));
         { E e; e.nar = nar; e.raw = A(c->feat, H4, W4); e.up = A(c->z2, H8, W8); e.up_nb = Bl; e.add1 = A(c->m, H4, W4); e.add1_nb = Bl;   // w2 = feat + m
           if (!nar) e.sum = A(c->w2, H4, W4); else e.add1 = nullptr;         // (the proxy pass stops at depth_encoder3: its w2 feeds nothing)
-          CR("depth_encoder3.enc2.3", false, CONV_S1, A(c->e3_2a, H4, W4), Bl, Bl, H4, W4, true, e); }
+          RUN(conv32_pair(c, st, false, "depth_encoder3.enc2.1", A(c->e3_1, H2, W2), Bl, Bl, H2, W2, raw(A(c->e3_2a, H4, W4)), "depth_encoder3.enc2.3", Bl, e)); }
 #undef CR
         return 0;
     };

@@ -447,7 +447,7 @@ static const Option kOptions[] = {
     {"fuse_first", &ptta_ctx::fuse_first, 2, false},    {"fuse_head_bwd", &ptta_ctx::fuse_head_bwd, 1, false},
     {"fuse_heads", &ptta_ctx::fuse_heads, 1, false},    {"heads_v2", &ptta_ctx::heads_v2, 1, false},
     {"cos_in_gemm", &ptta_ctx::cos_grad_fused, 1, false}, {"mask_bits", &ptta_ctx::mask_bits_on, 1, false},
-    {"stamps", &ptta_ctx::stamps, 1, true},
+    {"stamps", &ptta_ctx::stamps, 1, true},             {"pair_fuse", &ptta_ctx::pair_fuse, 1, true},
 };
 static const Option* find_option(const std::string& k) {
     for (const Option& o : kOptions) if (k == o.key) return &o;
@@ -474,6 +474,7 @@ int ptta_set_option(ptta_handle c, const char* key, int value) {
         return 0;
     }
     if (c->nl) return -38;                         // the generic engine has no other switch
+    if (k == "pair_fuse_count") return c->fail("ptta_set_option: 'pair_fuse_count' is read-only", -22);
     const Option* o = find_option(k);
     if (!o) return c->fail("ptta_set_option: unknown key '" + k + "'", -22);
     int* f = &(c->*(o->member));
@@ -506,6 +507,8 @@ int ptta_get_option(ptta_handle c, const char* key, int* value) {
     }
     if (c->nl) { if (k != "graph") return -38; *value = c->nl->use_graph; return 0; }
     if (k == "graph") { *value = c->use_graph; return 0; }
+    // read-only: how many (stride-2 -> stride-1) layer pairs the last step issued as ONE launch (a replayed graph: as it was captured)
+    if (k == "pair_fuse_count") { *value = c->pair_fuse_count; return 0; }
     const Option* o = find_option(k);
     if (!o) return -22;
     *value = c->*(o->member);

@@ -464,4 +464,80 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// ---- the tuned 32 -> 32 convolution kernels' shared pieces (conv32.hip, conv_pair.hip) ----------------------------------------
+// kernel parameters of one 32 -> 32 launch
+template <typename T>
+struct Conv32P {
+    const T* in; int in_nb;
+    const void* wpack;
+    const void* wpack2;          // lo fragments (bf16x3 arithmetic)
+    Epi<T> epi;
+    int B, Hin, Win, Hout, Wout;
+};
+
+__device__ __forceinline__ float4 relu4(float4 v) {
+    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    return v;
+}
+#define X3_TH 8
+#define X3_PW 34
+#define X3_PH 10
+
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef float float2_t __attribute__((ext_vector_type(2)));
+typedef short short2_t __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
+    float2_t v = {a, b};
+    const bf16x2_t h = __builtin_convertvector(v, bf16x2_t);          // v_cvt_pk_bf16_f32 (RNE)
+    hi = __builtin_bit_cast(unsigned, h);
+    float2_t r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
+    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_t));
+}
+// ReLU of two packed bf16: sign-magnitude values ordered as int16 -> one v_pk_max_i16 against zero (-0.0 -> +0.0)
+__device__ __forceinline__ unsigned relu_pk(unsigned v) {
+    const short2_t z = {0, 0};
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(short2_t, v), z));
+}
+
+// 8 consecutive channels of one NHWC pixel in registers
+template <typename T> struct Px;
+template <> struct Px<float> { float4 a, b; };
+template <> struct Px<bf16_t> { uint4 a; };
+template <typename T> __device__ __forceinline__ Px<T> px_zero();
+template <> __device__ __forceinline__ Px<float> px_zero<float>() { Px<float> r; r.a = make_float4(0.f, 0.f, 0.f, 0.f); r.b = r.a; return r; }
+template <> __device__ __forceinline__ Px<bf16_t> px_zero<bf16_t>() { Px<bf16_t> r; r.a = make_uint4(0u, 0u, 0u, 0u); return r; }
+__device__ __forceinline__ Px<float> px_load(const float* src) { Px<float> r; r.a = *(const float4*)src; r.b = *(const float4*)(src + 4); return r; }
+__device__ __forceinline__ Px<bf16_t> px_load(const bf16_t* src) { Px<bf16_t> r; r.a = *(const uint4*)src; return r; }
+// (ReLU,) bf16 hi / lo split, 16 B of hi fragments to `dst` and -- fp32 storage -- 16 B of lo fragments to `dst + lo_off`
+template <bool RELU>
+__device__ __forceinline__ void px_stage(const Px<float>& v, unsigned char* dst, int lo_off) {
+    float4 a0 = v.a, a1 = v.b;
+#ifdef X3_TIMING_NOSPLIT
+    // timing-only (wrong values): the staged pixel taken as if the producer had stored it split -- the upper bound of a pre-split storage format
+    *(float4*)dst = a0; *(float4*)(dst + lo_off) = a1; return;
+#endif
+    if (RELU) { a0 = relu4(a0); a1 = relu4(a1); }
+    uint4 hi, lo;
+    split2(a0.x, a0.y, hi.x, lo.x); split2(a0.z, a0.w, hi.y, lo.y);
+    split2(a1.x, a1.y, hi.z, lo.z); split2(a1.z, a1.w, hi.w, lo.w);
+    *(uint4*)dst = hi;
+    *(uint4*)(dst + lo_off) = lo;
+}
+template <bool RELU>
+__device__ __forceinline__ void px_stage(const Px<bf16_t>& v, unsigned char* dst, int) {
+    uint4 hi = v.a;
+    if (RELU) { hi.x = relu_pk(hi.x); hi.y = relu_pk(hi.y); hi.z = relu_pk(hi.z); hi.w = relu_pk(hi.w); }
+    *(uint4*)dst = hi;
+}
+// LDS pixel of the stride-1 halo tile: fp32 storage [hi 64 B | lo 64 B | pad 16 B], narrow [hi 64 B | pad 16 B]; both strides keep
+// ds_read_b128 of 16 consecutive pixels on disjoint banks (144: bank = 4 (9 p mod 16) + const; 80: 20 p mod 64 steps through all 16 quads)
+template <typename T> struct Geo;
+template <> struct Geo<float> { static constexpr int STR = 144, LO = 64, WL = 18 * 64 * 16, UPPX = 128, UPPC = 8; };
+template <> struct Geo<bf16_t> { static constexpr int STR = 80, LO = 0, WL = 0, UPPX = 64, UPPC = 4; };
+
+// staging item -> halo pixel: the 8 lanes of one ds_write_b128 group take pixels p and p+4 (not p, p+1):
+// at either pixel stride their footprints then fall on disjoint banks
+__device__ __forceinline__ int x3_stage_pix(int idx) { return ((idx >> 5) << 3) + (((idx >> 2) & 1) << 2) + ((idx >> 3) & 3); }
+
 #define PTTA_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)

@@ -104,6 +104,73 @@ int ptta_op_conv32(const float* in, const float* weight, const float* bias, floa
     return rc;
 }
 
+// Stand-alone (strided -> stride-1) pair of 32->32 3x3 convolutions on fp32 NHWC buffers (tests only), as the engine issues such a pair:
+// first layer: optional ReLU-mask (sign-bit words mask1_bits [b][hm][wm]) and addend add0 [b][hm][wm][32] -- its SUM is then what the second
+// layer reads; second layer: bilinear x2 skip `up` [b][hm/2][wm/2][32], skip addends add1 / add2, ReLU-mask mask2_bits (each may be null).
+// fused = 1: the one-launch form where it applies (conv_pair.hip), else -- and with fused = 0 -- the two launches; *fused_host tells which ran.
+// Outputs (each may be null): the second layer's map and sum, the first layer's map, sum and -- PTTA_DTYPE_F32 -- its sign-bit words.
+int ptta_op_conv32_pair(const float* in, const float* weight1, const float* bias1, const float* weight2, const float* bias2, const float* up,
+                        const float* add0, const float* add1, const float* add2, const uint32_t* mask1_bits, const uint32_t* mask2_bits,
+                        float* out_raw, float* out_sum, float* mid_raw, float* mid_sum, uint32_t* mid_bits, int b, int in_nb,
+                        int hin, int win, int first_mode, int relu1, int relu2, int in_major, int flip, int dtype, int w2, int fused,
+                        int* fused_host, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!in || !weight1 || !weight2 || (!out_raw && !out_sum) || b < 1 || in_nb < 1 || in_nb > b || hin < 1 || win < 1 ||
+        (first_mode != CONV_S2 && first_mode != CONV_T2) || (add2 && !add1) || (add1 && !out_sum)) return -22;
+    const bool nar = dtype != PTTA_DTYPE_F32;
+    if (w2 && (!nar || relu1 || relu2 || up)) return -22;           // (the hi + lo weight form exists for the narrow data gradients only)
+    const int hm = first_mode == CONV_S2 ? hin / 2 : hin * 2, wm = first_mode == CONV_S2 ? win / 2 : win * 2;
+    if (hm < 1 || wm < 1) return -22;
+    const long nin = (long)in_nb * hin * win * 32, nm = (long)b * hm * wm * 32, nu = (long)b * (hm / 2) * (wm / 2) * 32;
+    ScratchConvW sw1, sw2;
+    // device buffers in the storage type: [0] in, [1] up, [2] add0, [3] add1, [4] add2, [5] mid, [6] mid sum, [7] out_raw, [8] out_sum
+    void* t[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const long cnt[9] = {nin, up ? nu : 0, add0 ? nm : 0, add1 ? nm : 0, add2 ? nm : 0, nm, add0 ? nm : 0, out_raw ? nm : 0, out_sum ? nm : 0};
+    const float* src[5] = {in, up, add0, add1, add2};
+    const int es = nar ? 2 : 4;
+    int rc = (sw1.ok && sw2.ok) ? 0 : -12;
+    for (int k = 0; k < 9 && !rc; ++k) if (cnt[k] > 0 && hipMalloc(&t[k], (size_t)cnt[k] * es) != hipSuccess) rc = -12;
+    if (!rc) {
+        ptta_pack_conv32(weight1, sw1.w, in_major, flip, s);
+        ptta_pack_conv32(weight2, sw2.w, 0, 0, s);
+        for (int k = 0; k < 5; ++k) {
+            if (cnt[k] <= 0) continue;
+            if (nar) from_f32_launch(src[k], (bf16_t*)t[k], cnt[k], s);
+            else if (hipMemcpyAsync(t[k], src[k], (size_t)cnt[k] * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = -5;
+        }
+        (void)hipMemsetAsync(t[5], 0xff, (size_t)nm * es, s);         // (a fused launch that skipped a pixel of a side output shows as NaN)
+        if (t[6]) (void)hipMemsetAsync(t[6], 0xff, (size_t)nm * es, s);
+    }
+    if (!rc) {
+        Conv32Args f, g;
+        f.in = t[0]; f.in_nb = in_nb; f.w = &sw1.w; f.bias = bias1; f.out_raw = t[5]; f.B = b; f.Hin = hin; f.Win = win; f.mode = first_mode;
+        f.relu_in = relu1; f.bf16 = nar ? 1 : 0; f.x3 = 1; f.w2 = w2;
+        if (add0) { f.add1 = t[2]; f.add1_nb = b; f.out_sum = t[6]; }
+        if (mask1_bits) { f.mask = mask1_bits; f.mask_nb = b; f.mask_bits = mask1_bits; }      // (the kernels read the bit plane only)
+        if (!nar && mid_bits) { f.bits_out = mid_bits; f.bits_nb = b; }
+        g.in = add0 ? t[6] : t[5]; g.in_nb = b; g.w = &sw2.w; g.bias = bias2; g.up = t[1]; g.up_nb = b;
+        g.add1 = t[3]; g.add1_nb = b; g.add2 = t[4]; g.add2_nb = b;
+        if (mask2_bits) { g.mask = mask2_bits; g.mask_nb = b; g.mask_bits = mask2_bits; }
+        g.out_raw = t[7]; g.out_sum = t[8]; g.B = b; g.Hin = hm; g.Win = wm; g.mode = CONV_S1; g.relu_in = relu2; g.bf16 = nar ? 1 : 0; g.x3 = 1; g.w2 = w2;
+        int did = 0;
+        rc = fused ? ptta_launch_conv32_pair(f, g, s) : 1;
+        if (rc == 0) did = 1;
+        if (rc == 1) { rc = ptta_launch_conv32(f, s); if (!rc) rc = ptta_launch_conv32(g, s); }
+        if (fused_host) *fused_host = did;
+    }
+    if (!rc) {
+        float* dst[4] = {mid_raw, mid_sum, out_raw, out_sum};
+        for (int k = 0; k < 4; ++k) {
+            if (!dst[k] || !t[5 + k]) continue;
+            if (nar) to_f32_launch((const bf16_t*)t[5 + k], dst[k], nm, s);
+            else if (hipMemcpyAsync(dst[k], t[5 + k], (size_t)nm * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = -5;
+        }
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    for (int k = 0; k < 9; ++k) (void)hipFree(t[k]);
+    return rc;
+}
+
 // Stand-alone weight + bias gradient of a stride-1 3x3 convolution on dense fp32 NHWC maps (tests, tools/bench_gwgrad_wide.py): the
 // engine's launcher (impl 0), the fp32-MFMA form (1) or the direct fp32 form of PTTA_CONV_IMPL=naive (2), then `reps` more launches of
 // the same form timed with hipEvents on `s`.
