@@ -434,7 +434,7 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  * handle's streams and drops its captured graphs; the next step re-captures.  Every non-default value is a correct, slower form of
  * the same step, kept as the check of the default (tests/test_gpu_options.py) or taken by the library itself where the default
  * form does not apply (small maps, N > 16, SyncBatchNorm exchange).  Unknown key / value out of range: -22; a key the handle does
- * not have: -38 (the generic engine has "graph", "head_bn_fused" and, on PTTA_ADAPT_META_ONLY handles, "eval_bn_fused"; PTTA_DTYPE_MIXED handles keep every key but graph / aux_stream / thru / adam_in_wgrad / pair_fuse at 1).
+ * not have: -38 (the generic engine has "graph", "head_bn_fused" and, on PTTA_ADAPT_META_ONLY handles, "eval_bn_fused"; PTTA_DTYPE_MIXED handles keep every key but graph / aux_stream / thru / adam_in_wgrad / pair_fuse / tpair_fuse at 1).
  *   key             default  meaning of 0
  *   "graph"         0        (1:) ptta_step / ptta_step_pipelined / ptta_forward_eval replay captured hipGraphs from their second call on.  Default
  *                            since round 5: direct launches on the caller's stream and the handle's own streams -- measured FASTER than replay
@@ -460,6 +460,15 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  *                            stages 2 and 3 at 1/4 and 1/8 resolution, fp32 and narrow maps, and on PTTA_DTYPE_MIXED handles the three
  *                            stride-2 pairs of the data gradients).  Bit-identical (tests/test_gpu_conv_pair.py);
  *                            free on PTTA_DTYPE_MIXED handles
+ *   "tpair_fuse"    1        every (transposed -> stride-1) layer pair as two launches (1: ONE launch where the pair is an instantiated form,
+ *                            csrc/conv_tpair.hip, at every map size in the forward: the two decoder pairs of stage 2 on both chains and the two of
+ *                            decoder 3, fp32 and narrow maps; persistent 8 x 32 tiles where the stride-1 half would take them, 4 x 32 tiles on
+ *                            small maps.  The intermediate 32-channel map is then not written where nothing but the stride-1 layer reads its
+ *                            values -- always, unless the backward masks with the float map ("mask_bits" 0) -- and ptta_debug_tensor refuses
+ *                            "t2", "u2", "t3", "u3" with -38 while that holds.  On PTTA_DTYPE_MIXED handles also the data gradients' four
+ *                            transposed pairs of encoders 3 and 2, where a launch has at most one tile per block (480 tiles of 8 x 32: at
+ *                            352 x 1216, batch 1, the 1/4- and 1/2-resolution pairs; the full-resolution pair measured slower as one launch
+ *                            and stays two).  Bit-identical (tests/test_gpu_conv_tpair.py); free on PTTA_DTYPE_MIXED handles
  *   "stamps"        0        (diagnostic, 1:) fourteen one-thread nodes of the step's and the prefix's graphs write wall_clock64() ticks since
  *                            the step's first node into the debug tensor "stamps" -- where the branches of a replayed step start and end with
  *                            no profiler attached (tools/step_stamps.py, profiles/r05_step_stamps.txt); results unchanged
@@ -488,7 +497,8 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  *                       PTTA_CONV_IMPL=naive (no matrix-core convolution to ride in); -38 on MSG_CHN
  *   "pair_fuse_count"   how many layer pairs the last step issued as one launch ("pair_fuse"; a replayed graph: as it was captured); 0 with
  *                       "pair_fuse" 0, on maps too large for the form, with PTTA_CONV_IMPL=naive and PTTA_ARITH=exact
- * bit-identical to the default: aux_stream, thru, adam_in_wgrad, fuse_first, fuse_head_bwd, mask_bits, graph, pair_fuse; within bf16x3's own error (documented
+ *   "tpair_fuse_count"  the same count for "tpair_fuse"; 0 with "tpair_fuse" 0, with PTTA_CONV_IMPL=naive and PTTA_ARITH=exact
+ * bit-identical to the default: aux_stream, thru, adam_in_wgrad, fuse_first, fuse_head_bwd, mask_bits, graph, pair_fuse, tpair_fuse; within bf16x3's own error (documented
  * in the tests): fuse_heads, heads_v2, cos_in_gemm.
  * Environment, read once per ptta_create (csrc/ptta_kernels.h ptta_create_env) because it decides allocation and arithmetic:
  *   PTTA_CONV_IMPL=naive (direct fp32 kernels, PTTA_DTYPE_F32 only), PTTA_ARITH=exact (fp32 MFMA, MSG_CHN PTTA_DTYPE_F32 only),
@@ -511,7 +521,8 @@ int ptta_profile_read(ptta_handle h, int klass, double* ms_total_host, double* a
 /* Test / debug hooks (not on the hot path).  ptta_debug_tensor reads a named activation of the last forward.  With "head_bn_fused" 1 a head
  * forward does NOT write the raw convolution output in front of a fused BatchNorm2d (NLSPN "conv2.0.r1", CostDCNet "enc2d.layer1.0.r1", ...;
  * likewise "eval_bn_fused" and the eval forward of a PTTA_ADAPT_META_ONLY handle): such a name then returns what an earlier TTA forward left
- * there.  Set the option to 0 to read them. */
+ * there.  Set the option to 0 to read them.  With "tpair_fuse" 1 the MSG_CHN forward does not write the intermediate maps "t2", "u2", "t3", "u3" of its
+ * fused (transposed -> stride-1) pairs: reading one of them then FAILS with -38 instead of returning an earlier step's values; set "tpair_fuse" 0. */
 int ptta_debug_tensor(ptta_handle h, const char* name, float* dst, int64_t capacity, int64_t* numel_host, ptta_stream s);
 int ptta_op_conv32(const float* in_nhwc, const float* weight, const float* bias, float* out_nhwc,
                    int b, int hin, int win, int mode, int relu_in, int in_major, int flip, int dtype, int naive,
@@ -530,6 +541,17 @@ int ptta_op_conv32_pair(const float* in_nhwc, const float* weight1, const float*
                         const uint32_t* mask1_bits, const uint32_t* mask2_bits, float* out_raw, float* out_sum, float* mid_raw,
                         float* mid_sum, uint32_t* mid_bits, int b, int in_nb, int hin, int win, int first_mode, int relu1, int relu2,
                         int in_major, int flip, int dtype, int w2, int fused, int* fused_host, ptta_stream s);
+/* Test hook: the same pair and operand set with the one-launch form of csrc/conv_tpair.hip (a TRANSPOSED first half, first_mode 2; any other
+ * pair takes the two launches).  form 0 = as the step would choose by the map size, 1 = 4 x 32 one-tile blocks, 2 = persistent 8 x 32 tiles;
+ * max_blocks > 0 caps the grid, so that a small map makes a block walk several tiles (0: no cap).  With mid_raw NULL the one-launch form does
+ * not write the first layer's map (its sign-bit words still are); the hook then checks that the map's buffer still holds its fill (-14 if
+ * not).  form 0 also applies the step's rule of where the one launch pays (the data gradients' form: at most 480 tiles of 8 x 32).  *fused_host = 1 iff the one-launch form ran.  form outside 0 .. 2 or
+ * max_blocks < 0: -22.  Synchronises. */
+int ptta_op_conv32_tpair(const float* in_nhwc, const float* weight1, const float* bias1, const float* weight2, const float* bias2,
+                         const float* up_nhwc, const float* add0_nhwc, const float* add1_nhwc, const float* add2_nhwc,
+                         const uint32_t* mask1_bits, const uint32_t* mask2_bits, float* out_raw, float* out_sum, float* mid_raw,
+                         float* mid_sum, uint32_t* mid_bits, int b, int in_nb, int hin, int win, int first_mode, int relu1, int relu2,
+                         int in_major, int flip, int dtype, int w2, int fused, int form, int max_blocks, int* fused_host, ptta_stream s);
 /* Diagnostic (tests, tools/bench_gwgrad_wide.py): weight and bias gradient of a stride-1 3x3 convolution, dense fp32 NHWC device maps
  * x [b][h][w][ci] and gy [b][h][w][co], 1 <= ci, co <= 256 -> gw [co][ci][3][3], gb [co] (gb may be null).  impl 0: the launcher the engine
  * runs -- bf16x3 on the matrix cores (hi*hi + hi*lo + lo*hi, fp32 accumulation) for Ci, Co <= 64, 32 <-> 128 and, for channel counts that

@@ -7,6 +7,7 @@
 #include <map>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/ptta.h"
@@ -155,6 +156,9 @@ struct ptta_ctx : PrefixBufs {
     int fuse_first = 1, fuse_head_bwd = 1;
     int pair_fuse = 1;               // option "pair_fuse": each small-map stride-2 -> stride-1 layer pair as one launch (conv_pair.hip)
     int pair_fuse_count = 0;         // fused pair launches issued by the last step (read-only option "pair_fuse_count")
+    int tpair_fuse = 1;              // option "tpair_fuse": each transposed -> stride-1 layer pair of the forward as one launch (conv_tpair.hip)
+    int tpair_fuse_count = 0;        // fused transposed-pair launches issued by the last step (read-only option "tpair_fuse_count")
+    std::unordered_set<const void*> tpair_unwritten;     // intermediate maps the last fused launches did NOT write (ptta_debug_tensor refuses them)
     int cos_grad_fused = 1;          // PTTA_COS_IN_GEMM=0: the fused step writes d loss / d ref as a tensor (loss.hip cos_grad_body) instead
     bool cos_in_gemm = false;        // (set around the fused step's backward only: ptta_backward with a caller's gradient keeps the tensor form)
     void* w0frag = nullptr; float *hm_part = nullptr, *headP = nullptr; double* head_k12 = nullptr;
@@ -352,6 +356,10 @@ int conv32(ptta_ctx* c, hipStream_t s, const std::string& layer, bool bwd, int m
            int B, int Hin, int Win, bool relu, const E& e);
 int conv32_pair(ptta_ctx* c, hipStream_t s, bool bwd, const std::string& first, const void* in, int in_nb, int B, int Hin, int Win, const E& fe,
                 const std::string& second, int mid_nb, const E& se);
+int conv32_tpair(ptta_ctx* c, hipStream_t s, bool bwd, const std::string& first, const void* in, int in_nb, int B, int Hin, int Win, const E& fe,
+                 const std::string& second, int mid_nb, const E& se);
+bool conv32_tpair_takes(ptta_ctx* c, bool bwd, const std::string& first, const void* in, int in_nb, int B, int Hin, int Win, const E& fe,
+                        const std::string& second, int mid_nb, const E& se);
 int conv32w(ptta_ctx* c, hipStream_t s, const ConvW* w, const float* bias, const void* in, int in_nb, int B, int H, int W, const E& e);
 int conv32_first_bwd(ptta_ctx* c, hipStream_t s, const std::string& layer, ConvInArgs& f, int B, int H, int W, const E& e);
 int to_narrow(ptta_ctx* c, const void* src_f32, void* dst, long n, hipStream_t s);

@@ -120,6 +120,58 @@ int conv32_pair(ptta_ctx* c, hipStream_t s, bool bwd, const std::string& first, 
     return conv32(c, s, second, bwd, CONV_S1, mid, mid_nb, B, Hm, Wm, relu, se);
 }
 
+// A transposed layer and the stride-1 layer that consumes its output (`fe.sum` when the first layer has one, else `fe.raw`), forward (ReLU
+// on both inputs) or data gradients (bwd, no ReLU): ONE launch at every map size where the arithmetic is the default one, option
+// "tpair_fuse" is on and the pair's epilogue combination is instantiated (conv_tpair.hip); otherwise exactly the two conv32() calls.
+// Forward: nothing but the stride-1 layer reads the VALUES of the intermediate map -- the backward masks with its sign-bit words (real
+// frames, written by the fused launch as by the transposed one) and no other launch names it -- so the fused launch writes the map only
+// where the backward would read it as a float mask (no bit plane: option "mask_bits" 0); ptta_debug_tensor refuses such a map while
+// that holds (ptta_ctx::tpair_unwritten).  Data gradients: the first layer's SUM is still written (the side upsamplings read it).
+// (f, g: the two launches' arguments; returns whether the pair takes the one launch as the handle is configured now)
+static bool tpair_takes(ptta_ctx* c, Conv32Args& f, Conv32Args& g, bool bwd, const std::string& first, const void* in, int in_nb, int B, int Hin, int Win,
+                        const E& fe, const std::string& second, int mid_nb, const E& se) {
+    void* const mid = fe.sum ? fe.sum : fe.raw;
+    const bool nar = fe.nar || (bwd && c->nar_bwd);
+    if (!(c->tpair_fuse && !c->naive && (c->x3 || c->bf16 || nar) && fe.nar == se.nar && mid)) return false;
+    if (conv32_args(c, f, first, bwd, CONV_T2, in, in_nb, B, Hin, Win, !bwd, fe)) return false;
+    if (conv32_args(c, g, second, bwd, CONV_S1, mid, mid_nb, B, Hin * 2, Win * 2, !bwd, se)) return false;
+    return mid_nb == B && ptta_conv32_tpair_applies(f, g) && ptta_conv32_tpair_pays(f, g);
+}
+bool conv32_tpair_takes(ptta_ctx* c, bool bwd, const std::string& first, const void* in, int in_nb, int B, int Hin, int Win, const E& fe,
+                        const std::string& second, int mid_nb, const E& se) {
+    Conv32Args f, g;
+    return tpair_takes(c, f, g, bwd, first, in, in_nb, B, Hin, Win, fe, second, mid_nb, se);
+}
+int conv32_tpair(ptta_ctx* c, hipStream_t s, bool bwd, const std::string& first, const void* in, int in_nb, int B, int Hin, int Win, const E& fe,
+                 const std::string& second, int mid_nb, const E& se) {
+    const int Hm = Hin * 2, Wm = Win * 2;
+    const bool relu = !bwd;
+    void* const mid = fe.sum ? fe.sum : fe.raw;
+    const bool nar = fe.nar || (bwd && c->nar_bwd);
+    {
+        Conv32Args f, g;
+        if (tpair_takes(c, f, g, bwd, first, in, in_nb, B, Hin, Win, fe, second, mid_nb, se)) {
+            // the map's only other reader is a backward that masks with the float map: fp32 storage without a bit plane (where there is one it
+            // covers the real frames, the only ones the backward masks)
+            if (!bwd && (nar || f.bits_out != nullptr)) { f.out_raw = nullptr; c->tpair_unwritten.insert(fe.raw); }
+            else if (!bwd) c->tpair_unwritten.erase(fe.raw);
+            const int es_l = nar ? 2 : c->es;
+            double b1, m1, b2, m2;
+            conv32_cost(CONV_T2, B, Hin, Win, es_l, b1, m1); conv32_cost(CONV_S1, B, Hm, Wm, es_l, b2, m2);
+            // (both layers' algorithmic bytes and MACs as counted for the two launches: the launch executes both)
+            const bool small = (long)Hin * Win <= (long)c->H4 * c->W4;
+            ProfScope ps(c, 4 + (small ? 1 : 0), s, b1 + b2, m1 + m2, 1);
+            const int rc = ptta_launch_conv32_tpair(f, g, 0, 0, s);
+            if (rc == 1) return c->fail("conv32_tpair: fused form refused a case its own test accepted", -22);
+            if (rc == 0) c->tpair_fuse_count++;
+            return rc;
+        }
+    }
+    if (!bwd) c->tpair_unwritten.erase(fe.raw);
+    { const int rc = conv32(c, s, first, bwd, CONV_T2, in, in_nb, B, Hin, Win, relu, fe); if (rc) return rc; }
+    return conv32(c, s, second, bwd, CONV_S1, mid, mid_nb, B, Hm, Wm, relu, se);
+}
+
 int conv32w(ptta_ctx* c, hipStream_t s, const ConvW* w, const float* bias, const void* in, int in_nb, int B, int H, int W, const E& e) {
     Conv32Args a;
     a.in = in; a.in_nb = in_nb; a.w = w; a.bias = bias;
@@ -459,12 +511,11 @@ static int backbone(ptta_ctx* c, const float* image, bool train, hipStream_t s) 
           RUN(conv32_pair(c, st, false, "depth_encoder2.enc1.1", A(c->e2_0, H2, W2), Bl, Bl, H2, W2, raw(A(c->e2_1a, H4, W4)), "depth_encoder2.enc1.3", Bl, e)); }
         { E e; e.nar = nar; e.sum = A(c->z2, H8, W8); e.up = A(c->y2, H16, W16); e.up_nb = Bl; e.add1 = A(c->c3, H8, W8); e.add1_nb = Bl;            // z2 = e2_2 + c3
           RUN(conv32_pair(c, st, false, "depth_encoder2.enc2.1", A(c->e2_1, H4, W4), Bl, Bl, H4, W4, raw(A(c->e2_2a, H8, W8)), "depth_encoder2.enc2.3", Bl, e)); }
-        CR("depth_decoder2.dec2.1", false, CONV_T2, A(c->z2, H8, W8), Bl, Bl, H8, W8, true, raw(A(c->t2, H4, W4)));
+        // (each transposed layer and the stride-1 layer behind it: one launch, conv32_tpair)
         { E e; e.nar = nar; e.raw = A(c->z3, H4, W4); e.sum = A(c->s1_2, H4, W4); e.add1 = A(c->e2_1, H4, W4); e.add1_nb = Bl; e.add2 = A(c->m, H4, W4); e.add2_nb = Bl;
-          CR("depth_decoder2.dec2.3", false, CONV_S1, A(c->t2, H4, W4), Bl, Bl, H4, W4, true, e); }
-        CR("depth_decoder2.dec1.1", false, CONV_T2, A(c->s1_2, H4, W4), Bl, Bl, H4, W4, true, raw(A(c->u2, H2, W2)));
+          RUN(conv32_tpair(c, st, false, "depth_decoder2.dec2.1", A(c->z2, H8, W8), Bl, Bl, H8, W8, raw(A(c->t2, H4, W4)), "depth_decoder2.dec2.3", Bl, e)); }
         { E e; e.nar = nar; e.raw = A(c->z4, H2, W2); e.sum = A(c->s0_2, H2, W2); e.add1 = A(c->e2_0, H2, W2); e.add1_nb = Bl; e.add2 = A(c->c1, H2, W2); e.add2_nb = Bl;
-          CR("depth_decoder2.dec1.3", false, CONV_S1, A(c->u2, H2, W2), Bl, Bl, H2, W2, true, e); }
+          RUN(conv32_tpair(c, st, false, "depth_decoder2.dec1.1", A(c->s1_2, H4, W4), Bl, Bl, H4, W4, raw(A(c->u2, H2, W2)), "depth_decoder2.dec1.3", Bl, e)); }
         CR("depth_decoder2.prdct.1", false, CONV_S1, A(c->s0_2, H2, W2), Bl, Bl, H2, W2, true, raw(A(c->v2, H2, W2)));
         {
             const LOut& lo = c->lout["depth_decoder2.prdct.3"];
@@ -527,12 +578,10 @@ static int backbone(ptta_ctx* c, const float* image, bool train, hipStream_t s) 
     // decoder 3: real frames only (the proxy pass stops at depth_encoder3, :509-532); the stage-2 head forward stops at
     // depth_encoder3 for both passes (:652,:676)
     if (!c->skip_dec3) {
-    CV("depth_decoder3.dec2.1", false, CONV_T2, c->w2, B2, Nn, H4, W4, true, e_raw(c->t3));
     { E e; e.sum = c->s1_3; e.add1 = c->e3_1; e.add1_nb = B2; e.add2 = c->c1; e.add2_nb = B2;
-      CV("depth_decoder3.dec2.3", false, CONV_S1, c->t3, Nn, Nn, H2, W2, true, e); }
-    CV("depth_decoder3.dec1.1", false, CONV_T2, c->s1_3, Nn, Nn, H2, W2, true, e_raw(c->u3));
+      RUN(conv32_tpair(c, s, false, "depth_decoder3.dec2.1", c->w2, B2, Nn, H4, W4, e_raw(c->t3), "depth_decoder3.dec2.3", Nn, e)); }
     { E e; e.sum = c->s0_3; e.add1 = c->e3_0; e.add1_nb = B2; e.add2 = c->c0; e.add2_nb = B2;
-      CV("depth_decoder3.dec1.3", false, CONV_S1, c->u3, Nn, Nn, H1, W1, true, e); }
+      RUN(conv32_tpair(c, s, false, "depth_decoder3.dec1.1", c->s1_3, Nn, Nn, H2, W2, e_raw(c->u3), "depth_decoder3.dec1.3", Nn, e)); }
     CV("depth_decoder3.prdct.1", false, CONV_S1, c->s0_3, Nn, Nn, H1, W1, true, e_raw(c->v3));
     {
         const LOut& lo = c->lout["depth_decoder3.prdct.3"];

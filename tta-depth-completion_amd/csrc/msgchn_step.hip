@@ -168,6 +168,7 @@ static bool thru_ok(ptta_ctx* c, hipStream_t s) {
 static int step_body(ptta_handle c, const float* image, const float* loss_image, const float* sparse, const float* validity,
                      ptta_stream s_) {
     c->pair_fuse_count = 0;                                  // (option "pair_fuse_count": the fused pair launches of this step as enqueued or captured)
+    c->tpair_fuse_count = 0;                                 // (option "tpair_fuse_count", likewise)
     RUN(ensure_fused_heads(c, (hipStream_t)s_));             // (before thru_ok: the direct-launch step would otherwise take the joined tail on its first call only)
     c->thru_active = thru_ok(c, (hipStream_t)s_);
     c->cnt_sparse = c->thru_active ? sparse : nullptr; c->cnt_validity = validity;

@@ -448,6 +448,7 @@ static const Option kOptions[] = {
     {"fuse_heads", &ptta_ctx::fuse_heads, 1, false},    {"heads_v2", &ptta_ctx::heads_v2, 1, false},
     {"cos_in_gemm", &ptta_ctx::cos_grad_fused, 1, false}, {"mask_bits", &ptta_ctx::mask_bits_on, 1, false},
     {"stamps", &ptta_ctx::stamps, 1, true},             {"pair_fuse", &ptta_ctx::pair_fuse, 1, true},
+    {"tpair_fuse", &ptta_ctx::tpair_fuse, 1, true},
 };
 static const Option* find_option(const std::string& k) {
     for (const Option& o : kOptions) if (k == o.key) return &o;
@@ -474,7 +475,7 @@ int ptta_set_option(ptta_handle c, const char* key, int value) {
         return 0;
     }
     if (c->nl) return -38;                         // the generic engine has no other switch
-    if (k == "pair_fuse_count") return c->fail("ptta_set_option: 'pair_fuse_count' is read-only", -22);
+    if (k == "pair_fuse_count" || k == "tpair_fuse_count") return c->fail("ptta_set_option: '" + k + "' is read-only", -22);
     const Option* o = find_option(k);
     if (!o) return c->fail("ptta_set_option: unknown key '" + k + "'", -22);
     int* f = &(c->*(o->member));
@@ -509,6 +510,8 @@ int ptta_get_option(ptta_handle c, const char* key, int* value) {
     if (k == "graph") { *value = c->use_graph; return 0; }
     // read-only: how many (stride-2 -> stride-1) layer pairs the last step issued as ONE launch (a replayed graph: as it was captured)
     if (k == "pair_fuse_count") { *value = c->pair_fuse_count; return 0; }
+    // read-only: the same count for the (transposed -> stride-1) pairs of option "tpair_fuse"
+    if (k == "tpair_fuse_count") { *value = c->tpair_fuse_count; return 0; }
     const Option* o = find_option(k);
     if (!o) return -22;
     *value = c->*(o->member);
@@ -579,6 +582,8 @@ int ptta_debug_tensor(ptta_handle c, const char* name, float* dst, int64_t capac
     if (it == c->dbg.end()) return c->fail(std::string("no debug tensor ") + name, -2);
     if (numel_host) *numel_host = it->second.numel;
     if (!dst) return 0;
+    if (c->tpair_unwritten.count(it->second.p))
+        return c->fail(std::string("debug tensor ") + name + " is not written while option 'tpair_fuse' is 1 (the fused launch keeps it on chip): set it to 0", -38);
     if (capacity < it->second.numel) return c->fail("capacity too small", -22);
     hipStream_t s = (hipStream_t)s_;
     const long n = it->second.numel;

@@ -50,6 +50,12 @@ int ptta_launch_conv32(const Conv32Args& a, hipStream_t s);
 // a stride-2 convolution and the stride-1 convolution that consumes it, on a small map, in one launch (conv_pair.hip); returns 1 when not applicable
 bool ptta_conv32_pair_applies(const Conv32Args& first, const Conv32Args& second);
 int ptta_launch_conv32_pair(const Conv32Args& first, const Conv32Args& second, hipStream_t s);
+// a transposed convolution and the stride-1 convolution that consumes it in one launch, at every map size (conv_tpair.hip); returns 1 when
+// not applicable.  first.out_raw may be null (the intermediate map is then not written); form 0 / 1 / 2: by the map size / 4 x 32 tiles /
+// persistent 8 x 32 tiles; max_blocks > 0 caps the grid
+bool ptta_conv32_tpair_applies(const Conv32Args& first, const Conv32Args& second);
+bool ptta_conv32_tpair_pays(const Conv32Args& first, const Conv32Args& second);      // form 0: the sites where the one launch measured faster
+int ptta_launch_conv32_tpair(const Conv32Args& first, const Conv32Args& second, int form, int max_blocks, hipStream_t s);
 // layer-loop trial (conv32.hip conv32_s1_small_loop_kernel; tools/bench_chain.py): `reps` dependent plain stride-1 layers in one launch
 int ptta_launch_conv32_loop(const Conv32Args& a, void* buf_a, void* buf_b, int reps, unsigned* ctr, unsigned* base_io, int* err, int variant, hipStream_t s);
 

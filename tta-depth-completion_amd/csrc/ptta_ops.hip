@@ -109,11 +109,12 @@ int ptta_op_conv32(const float* in, const float* weight, const float* bias, floa
 // layer reads; second layer: bilinear x2 skip `up` [b][hm/2][wm/2][32], skip addends add1 / add2, ReLU-mask mask2_bits (each may be null).
 // fused = 1: the one-launch form where it applies (conv_pair.hip), else -- and with fused = 0 -- the two launches; *fused_host tells which ran.
 // Outputs (each may be null): the second layer's map and sum, the first layer's map, sum and -- PTTA_DTYPE_F32 -- its sign-bit words.
-int ptta_op_conv32_pair(const float* in, const float* weight1, const float* bias1, const float* weight2, const float* bias2, const float* up,
-                        const float* add0, const float* add1, const float* add2, const uint32_t* mask1_bits, const uint32_t* mask2_bits,
-                        float* out_raw, float* out_sum, float* mid_raw, float* mid_sum, uint32_t* mid_bits, int b, int in_nb,
-                        int hin, int win, int first_mode, int relu1, int relu2, int in_major, int flip, int dtype, int w2, int fused,
-                        int* fused_host, ptta_stream s_) {
+// (tform < 0: the one-launch form of conv_pair.hip; tform 0 / 1 / 2: that of conv_tpair.hip in this form, its grid capped at max_blocks)
+static int op_conv32_pair_body(const float* in, const float* weight1, const float* bias1, const float* weight2, const float* bias2, const float* up,
+                               const float* add0, const float* add1, const float* add2, const uint32_t* mask1_bits, const uint32_t* mask2_bits,
+                               float* out_raw, float* out_sum, float* mid_raw, float* mid_sum, uint32_t* mid_bits, int b, int in_nb,
+                               int hin, int win, int first_mode, int relu1, int relu2, int in_major, int flip, int dtype, int w2, int fused,
+                               int* fused_host, int tform, int max_blocks, ptta_stream s_) {
     hipStream_t s = (hipStream_t)s_;
     if (!in || !weight1 || !weight2 || (!out_raw && !out_sum) || b < 1 || in_nb < 1 || in_nb > b || hin < 1 || win < 1 ||
         (first_mode != CONV_S2 && first_mode != CONV_T2) || (add2 && !add1) || (add1 && !out_sum)) return -22;
@@ -153,8 +154,20 @@ int ptta_op_conv32_pair(const float* in, const float* weight1, const float* bias
         if (mask2_bits) { g.mask = mask2_bits; g.mask_nb = b; g.mask_bits = mask2_bits; }
         g.out_raw = t[7]; g.out_sum = t[8]; g.B = b; g.Hin = hm; g.Win = wm; g.mode = CONV_S1; g.relu_in = relu2; g.bf16 = nar ? 1 : 0; g.x3 = 1; g.w2 = w2;
         int did = 0;
-        rc = fused ? ptta_launch_conv32_pair(f, g, s) : 1;
+        if (!fused) rc = 1;
+        else if (tform < 0) rc = ptta_launch_conv32_pair(f, g, s);
+        else {
+            Conv32Args ff = f;
+            if (!mid_raw) ff.out_raw = nullptr;                      // (no reader of the first half's map: the one-launch form does not write it)
+            rc = ptta_launch_conv32_tpair(ff, g, tform, max_blocks, s);
+        }
         if (rc == 0) did = 1;
+        if (rc == 0 && tform >= 0 && !mid_raw) {
+            // the one-launch form was told not to write the first half's map: its buffer must still hold the fill
+            std::vector<unsigned char> hb((size_t)nm * es);
+            if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(hb.data(), t[5], hb.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = -5;
+            else for (unsigned char ch : hb) if (ch != 0xff) { rc = -14; break; }
+        }
         if (rc == 1) { rc = ptta_launch_conv32(f, s); if (!rc) rc = ptta_launch_conv32(g, s); }
         if (fused_host) *fused_host = did;
     }
@@ -169,6 +182,27 @@ int ptta_op_conv32_pair(const float* in, const float* weight1, const float* bias
     if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
     for (int k = 0; k < 9; ++k) (void)hipFree(t[k]);
     return rc;
+}
+
+int ptta_op_conv32_pair(const float* in, const float* weight1, const float* bias1, const float* weight2, const float* bias2, const float* up,
+                        const float* add0, const float* add1, const float* add2, const uint32_t* mask1_bits, const uint32_t* mask2_bits,
+                        float* out_raw, float* out_sum, float* mid_raw, float* mid_sum, uint32_t* mid_bits, int b, int in_nb,
+                        int hin, int win, int first_mode, int relu1, int relu2, int in_major, int flip, int dtype, int w2, int fused,
+                        int* fused_host, ptta_stream s_) {
+    return op_conv32_pair_body(in, weight1, bias1, weight2, bias2, up, add0, add1, add2, mask1_bits, mask2_bits, out_raw, out_sum, mid_raw, mid_sum,
+                               mid_bits, b, in_nb, hin, win, first_mode, relu1, relu2, in_major, flip, dtype, w2, fused, fused_host, -1, 0, s_);
+}
+// The same pair with the one-launch form of conv_tpair.hip (a TRANSPOSED first half): form 0 = as the step would choose by the map size,
+// 1 = 4 x 32 one-tile blocks, 2 = persistent 8 x 32 tiles; max_blocks > 0 caps the grid so that a small map makes a block walk several
+// tiles.  With mid_raw null the one-launch form does not write the first half's map (its sign-bit words still are).
+int ptta_op_conv32_tpair(const float* in, const float* weight1, const float* bias1, const float* weight2, const float* bias2, const float* up,
+                         const float* add0, const float* add1, const float* add2, const uint32_t* mask1_bits, const uint32_t* mask2_bits,
+                         float* out_raw, float* out_sum, float* mid_raw, float* mid_sum, uint32_t* mid_bits, int b, int in_nb,
+                         int hin, int win, int first_mode, int relu1, int relu2, int in_major, int flip, int dtype, int w2, int fused,
+                         int form, int max_blocks, int* fused_host, ptta_stream s_) {
+    if (form < 0 || form > 2 || max_blocks < 0) return -22;
+    return op_conv32_pair_body(in, weight1, bias1, weight2, bias2, up, add0, add1, add2, mask1_bits, mask2_bits, out_raw, out_sum, mid_raw, mid_sum,
+                               mid_bits, b, in_nb, hin, win, first_mode, relu1, relu2, in_major, flip, dtype, w2, fused, fused_host, form, max_blocks, s_);
 }
 
 // Stand-alone weight + bias gradient of a stride-1 3x3 convolution on dense fp32 NHWC maps (tests, tools/bench_gwgrad_wide.py): the

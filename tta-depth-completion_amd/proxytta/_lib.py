@@ -131,6 +131,7 @@ SIGNATURES = [
     ('ptta_op_conv32', c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     ('ptta_op_conv32_chain', c_int, [_P] * 6 + [c_int] * 7 + [POINTER(c_float), _P]),
     ('ptta_op_conv32_pair', c_int, [_P] * 16 + [c_int] * 12 + [POINTER(c_int), _P]),
+    ('ptta_op_conv32_tpair', c_int, [_P] * 16 + [c_int] * 14 + [POINTER(c_int), _P]),
     ('ptta_op_gwgrad', c_int, [_P, _P, _P, _P] + [c_int] * 7 + [POINTER(c_float), _P]),
     ('ptta_op_gconv', c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, _P, _P] + [c_int] * 16 + [POINTER(ctypes.c_double), POINTER(c_int), _P]),
     ('ptta_op_gconv_affine', c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, _P, _P] + [c_int] * 16 + [POINTER(ctypes.c_double), POINTER(c_int),

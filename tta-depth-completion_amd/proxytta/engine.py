@@ -456,7 +456,7 @@ class Engine:
 
     def set_option(self, key, value):
         """Per-handle switch (include/ptta.h ptta_set_option: graph, aux_stream, thru, fuse_first, fuse_head_bwd, fuse_heads, heads_v2,
-        cos_in_gemm, mask_bits, stamps, pair_fuse; eval_bn_fused, head_bn_fused on the generic engine's handles)."""
+        cos_in_gemm, mask_bits, stamps, pair_fuse, tpair_fuse; eval_bn_fused, head_bn_fused on the generic engine's handles)."""
         self._chk(self.lib.ptta_set_option(self.handle, key.encode(), int(value)), 'ptta_set_option(%s)' % key)
 
     def get_option(self, key):
