@@ -133,7 +133,28 @@ enum { PTTA_NLSPN_LEGACY_OFFSET = 0x100,
         * block's own BatchNorm2d while still listing its gamma / beta: separate work); PTTA_DTYPE_MIXED (no bound measured);
         * PTTA_NLSPN_SYNCBN_ADAPT.  On such a handle ptta_set_stat_sync, ptta_set_stat_sync_rccl and ptta_set_grad_sync_rccl return -38 and leave it
         * unchanged (one rank only). */
-       PTTA_ADAPT_META_ONLY = 0x400 };
+       PTTA_ADAPT_META_ONLY = 0x400,
+       /* CostDCNet, OR-ed into PTTA_META_1LAYER: the network without the meta layer, CostDCNet._forward (external_src/costdcnet/CostDCNet_adapt.py:
+        * 177-205) -- what loss_type 'pretrain' (the reference's default) runs: Encoder2D -> fusion -> UNet3D -> regression, no conv1_rgb_meta, no
+        * zero-image pass, no heads (ptta_embedding_rows() is 0).  fp32, one rank.  (PTTA_META_NONE with PTTA_BACKBONE_COSTDCNET stays refused.)
+        *   PTTA_COSTDC_PLAIN | PTTA_ADAPT_META_ONLY: the source model, the loaded checkpoint before any adaptation.  ptta_adapted_count() is 0;
+        *     ptta_forward_eval only: EVERY BatchNorm normalises with its loaded running statistics -- Encoder2D's 15 BatchNorm2d (kept by
+        *     ptta_load_weights on this handle) and the UNet3D's 28 BatchNorm3d + ELU as constant affines in the epilogues of the convolutions in
+        *     front of them (option "eval_bn_fused", default 1; "eval_bn_fused_count" reads 43), the sparse encoder's nine as their own launches.
+        *     The tables are built once per load; a state dict without one of the buffers loads, and the first ptta_forward_eval returns -3 naming
+        *     the missing tensor.  ptta_load_weights accepts and ignores conv1_rgb_meta.*, proj* and pred* (a stage-3 checkpoint holds them).
+        *     ptta_forward_train, ptta_step, ptta_backward and ptta_adam_step return -38 and leave the handle usable; so do ptta_head_* and the
+        *     three exchange setters.  The dual-corner padding works as on the ProxyTTA handle.
+        *   PTTA_COSTDC_PLAIN alone: the BatchNorm-adaptation baseline, adapt_parameters('meta_bn') on a model whose head was never prepared
+        *     (src/costdcnet_model_adapt.py:357-378).  ptta_adapted_count() is 30: gamma / beta of Encoder2D's 15 BatchNorm2d in the order of the
+        *     32-entry list minus conv1_rgb_meta.*; ptta_adapted_repeat() is 1.  A training forward is ONE pass: emb_out, ref_out of
+        *     ptta_forward_train and grad_ref of ptta_backward must be NULL, loss_info[3] is exactly 0, and activations are allocated for n frames,
+        *     not 2 n.  BatchNorm2d uses batch statistics in train and eval forwards (its running statistics are dropped); BatchNorm3d and the
+        *     sparse encoder's BatchNorm use batch statistics in train mode and update their bound running statistics ONCE per training forward
+        *     (num_batches_tracked + 1, where the ProxyTTA handle's two passes add 2), and use them in eval.  "eval_bn_fused" is -38 (no constant
+        *     affine).  ptta_head_* and the three exchange setters return -38.
+        * Refused with -38 and a reason in ptta_last_error(NULL): another backbone, PTTA_META_2LAYERS, PTTA_SYNCBN_ADAPT, PTTA_DTYPE_MIXED. */
+       PTTA_COSTDC_PLAIN = 0x800 };
 
 /* Hyper-parameters of the step.  Reference: src/tta.py:10-160 flags learning_rates,
  * optimizer_betas, optimizer_epsilon, w_weight_decay, w_loss_sparse_depth, w_loss_smoothness,
@@ -474,7 +495,9 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  *                            no profiler attached (tools/step_stamps.py, profiles/r05_step_stamps.txt); results unchanged
  *   "eval_bn_fused" 1        (PTTA_ADAPT_META_ONLY handles only, the source model PTTA_META_NONE | PTTA_ADAPT_META_ONLY among them; -38 elsewhere) 0: every BatchNorm2d of the eval forward is its own apply launch
  *                            from the same affine table (1: in the epilogue of the convolution in front of it).  Bit-identical
- *                            (tests/test_gpu_nlspn_meta.py): both forms compute fmaf(conv + bias, scale, shift)
+ *                            (tests/test_gpu_nlspn_meta.py): both forms compute fmaf(conv + bias, scale, shift).  On CostDCNet's source model
+ *                            (PTTA_COSTDC_PLAIN | PTTA_ADAPT_META_ONLY) the switch covers the 28 BatchNorm3d + ELU as well
+ *                            (tests/test_gpu_costdc_source.py)
  *   "head_bn_fused" 1        (NLSPN and CostDCNet handles; -38 on MSG_CHN, which has no BatchNorm2d) 0: in the stage-2 head trainer's two
  *                            no-gradient backbone passes (ptta_head_forward / ptta_head_step, both forms of ptta_head_set_form) every frozen
  *                            BatchNorm2d is an affine-table launch and an apply launch of its own (1: all tables of the prefix are built by ONE
@@ -495,6 +518,8 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  *   "head_bn_fused_count"  how many BatchNorm2d of this handle's stage-2 prefix ride in a convolution epilogue as configured now: 36 (NLSPN),
  *                       38 (NLSPN 2layers), 15 (CostDCNet), 17 (CostDCNet 2layers); 0 with "head_bn_fused" 0, on a PTTA_DTYPE_MIXED handle and with
  *                       PTTA_CONV_IMPL=naive (no matrix-core convolution to ride in); -38 on MSG_CHN
+ *   "eval_bn_fused_count"  (PTTA_ADAPT_META_ONLY handles; -38 elsewhere) how many BatchNorm of the eval forward ride in a convolution epilogue as
+ *                       configured now: 43 on CostDCNet's source model (15 BatchNorm2d + 28 BatchNorm3d); 0 with "eval_bn_fused" 0
  *   "pair_fuse_count"   how many layer pairs the last step issued as one launch ("pair_fuse"; a replayed graph: as it was captured); 0 with
  *                       "pair_fuse" 0, on maps too large for the form, with PTTA_CONV_IMPL=naive and PTTA_ARITH=exact
  *   "tpair_fuse_count"  the same count for "tpair_fuse"; 0 with "tpair_fuse" 0, with PTTA_CONV_IMPL=naive and PTTA_ARITH=exact
@@ -594,12 +619,15 @@ int ptta_op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, int
  *   y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res])                    no flag; with res: act 1, the BasicBlock's ReLU behind the sum
  *   y = relu(relu(fmaf(conv + bias, scale[c], shift[c])) + res)               PTTA_GCONV_AFF_ACT_FIRST: CostDCNet's ResBlock; res and act 1 required
  *   y = fmaf(conv + bias, scale[c], shift[c]) + res                           PTTA_GCONV_AFF_RES_PLAIN: the 2layers block's last BatchNorm2d; res and act 0
+ *   v = fmaf(conv + bias, scale[c], shift[c]); y = v > 0 ? v : expm1f(v)      act 4 (ELU), no flag or PTTA_GCONV_VERT: CostDCNet's BatchNorm3d + ELU behind
+ *                                                                             its 1x3x3 / 3x1x1 convolution (the source model's eval forward); PTTA_GCONV_S1,
+ *                                                                             k = 3, no res; bf16x3 and, below six_b, bf16x6 (tests/test_gpu_gconv_affine_elu.py)
  * scale / shift [co]: the {scale, shift} rows of an eval affine table (what PTTA_GBN_EVAL leaves in st + 2 co and st + 3 co), 16-byte
  * aligned; res: the residual, a view [b][hout][wout] of co channels with pixel stride ld_res >= co, or NULL with ld_res 0.
  * Bit-identical to ptta_op_gconv with act 0 and the same six_b followed by ptta_op_gbn in mode PTTA_GBN_EVAL with the same act and, with a
  * residual, act_first 0 / res_relu 1 (no flag), act_first 1 / res_relu 1 (ACT_FIRST), act_first 0 / res_relu 0 (RES_PLAIN)
  * (tests/test_gpu_gconv_affine.py, tests/test_gpu_gconv_affine_forms.py).  Matrix-core forms only: impl 0, c0 and c1 multiples of 8
- * (PTTA_GCONV_S1) or 16, act 0 / 1 / 2, no accumulate, no statistics, no PTTA_GCONV_DGRAD.  six_b as in ptta_op_gconv: the images below it
+ * (PTTA_GCONV_S1) or 16, act 0 / 1 / 2 (4 as stated above; ptta_op_gconv itself refuses 4), no accumulate, no statistics, no PTTA_GCONV_DGRAD.  six_b as in ptta_op_gconv: the images below it
  * bf16x6, with every form above, on PTTA_GCONV_S1 and every launch form of PTTA_GCONV_S2.  PTTA_GCONV_T2 has the first form in bf16x3 only
  * (no stage-2 prefix holds a transposed layer).  -22 BEFORE any launch for anything else: ACT_FIRST without res or with an activation other
  * than ReLU, RES_PLAIN without res or with an activation, both flags, six_b > b, a NULL or misaligned scale / shift, res without ld_res (or

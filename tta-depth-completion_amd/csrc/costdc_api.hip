@@ -18,6 +18,11 @@
 //     BatchNorm3d's running statistics with the proxy pass too;
 //   1x1x1 classifier -> per-plane pixel shuffle + softmax + expected plane (CD:408-424) x z_step;
 //   heads: proj / pred on the proxy pass's bottleneck rows, proj_t on the real pass's (CD:243-251).
+// No meta layer (PTTA_COSTDC_PLAIN; CostDCNet._forward, CD:177-205, what loss_type 'pretrain' runs): enc2d.conv2 writes the fused
+//   volume's 2-D features itself, one pass (gnet.h GNet::one_pass), no heads.  With PTTA_ADAPT_META_ONLY it is the source model: nothing
+//   adapts, eval forward only, EVERY BatchNorm from its loaded running statistics -- the 15 BatchNorm2d and the 28 BatchNorm3d + ELU in their
+//   convolutions' epilogues (GNet::eval_const_all, option "eval_bn_fused"); the sparse encoder's nine keep their own launches (its stream runs
+//   beside Encoder2D and is latency-bound).
 // Backward = the op list in reverse (data gradients through the frozen UNet3D and Encoder2D, BatchNorm2d gamma/beta
 // gradients, weight gradient of the meta conv), then Adam on device.
 #include "gnet.h"
@@ -43,6 +48,7 @@ struct costdc_engine : GNet {
     // (src/tta_main.py:326,339), so every BatchNorm of the model is adapted and has lost its running statistics (AD:364-372)
     int sync_adapt = 0;
     int meta2 = 0;                                    // the 2layers meta block instead of the 1layer conv
+    int plain = 0;                                    // no meta layer, one pass, no heads (PTTA_COSTDC_PLAIN)
     std::map<std::string, std::pair<int, int>> sbn_ad;
     float* sgrad[4] = {nullptr, nullptr, nullptr, nullptr};
     float* sp_bw = nullptr;
@@ -58,14 +64,15 @@ struct costdc_engine : GNet {
     std::map<std::string, SConv> sconv;
     std::map<std::string, SBn> sbn;
 
-    long rows() const override { return (long)N * fh * fw; }
+    long rows() const override { return plain ? 0 : (long)N * fh * fw; }
     int emb_dim() const override { return 512; }
 
     // one P3D block (unet3d.py:66-84) on a volume of D planes of h x w: returns the output tensor
     int p3d(const std::string& name, int x0, int x1, int cout, int D, int h, int w) {
         const int per = N * D;
-        const int r1 = tensor(name + ".r1", 2 * per, h, w, cout, true, per), a1 = tensor(name + ".a1", 2 * per, h, w, cout, true, per);
-        const int r2 = tensor(name + ".r2", 2 * per, h, w, cout, true, per), a2 = tensor(name + ".a2", 2 * per, h, w, cout, true, per);
+        const int np = passes(W_BOTH, true) * per;
+        const int r1 = tensor(name + ".r1", np, h, w, cout, true, per), a1 = tensor(name + ".a1", np, h, w, cout, true, per);
+        const int r2 = tensor(name + ".r2", np, h, w, cout, true, per), a2 = tensor(name + ".a2", np, h, w, cout, true, per);
         conv(name + ".conv1", x0, x1, r1, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH);
         bn(name + ".bn1", r1, a1, -1, GACT_ELU, W_BOTH, !sync_adapt).tracked = !sync_adapt;
         { Op& c2 = conv(name + ".conv2", a1, -1, r2, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH); c2.rH = D; c2.rW = h * w; }
@@ -79,15 +86,16 @@ struct costdc_engine : GNet {
     }
 
     void build() {
-        const int N2 = 2 * N;
+        const int P2 = passes(W_BOTH, true), N2 = P2 * N;         // no meta layer: one pass, tensors for N frames
         h4 = H / 4; w4 = W / 4;
         // adapt_parameters('meta_bn') order: parameters with 'meta' in the name first (AD:358-364), then BatchNorm2d affine
         // parameters in module order (AD:365-378)
         const std::string MP = "conv1_rgb_meta.conv1_meta";
         int ad_mw = -1, ad_mb = -1, ad_w1 = -1;
-        if (!meta2) {
+        const bool fz = plain && meta_only;              // the source model: every BatchNorm2d keeps its loaded gamma / beta
+        if (!plain && !meta2) {
             ad_mw = add_adapted("conv1_rgb_meta.weight", 16L * 16 * 9); ad_mb = add_adapted("conv1_rgb_meta.bias", 16);
-        } else {
+        } else if (!plain) {
             // Res_Conv's seven parameters in named_parameters order; its two BatchNorm2d come again at the end of the BatchNorm pass
             // (the block is registered last, by _prepare_head): torch.optim.Adam steps those four twice per step()
             ad_w1 = add_adapted(MP + ".0.0.weight", 64L * 16 * 9);
@@ -100,7 +108,7 @@ struct costdc_engine : GNet {
         const int c1r = tensor("enc2d.c1.r", N2, H, W, 64, true), c1 = tensor("enc2d.c1", N2, H, W, 64, true);
         conv("enc2d.conv1", t_in, -1, c1r, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH, false, false);
         if (!naive) convs["enc2d.conv1"].Ci_real = 4;
-        bn("enc2d.norm1", c1r, c1, -1, GACT_RELU, W_BOTH);
+        bn("enc2d.norm1", c1r, c1, -1, GACT_RELU, W_BOTH, fz);
         int cur = c1, hh = H, ww = W;
         const int planes[3] = {64, 96, 128}, strides[3] = {1, 2, 2};
         for (int li = 0; li < 3; ++li)
@@ -111,28 +119,28 @@ struct costdc_engine : GNet {
                 const int r1 = tensor(P + ".r1", N2, ho, wo, C, true), a1 = tensor(P + ".a1", N2, ho, wo, C, true);
                 const int r2 = tensor(P + ".r2", N2, ho, wo, C, true), out = tensor(P + ".out", N2, ho, wo, C, true);
                 conv(P + ".conv1", cur, -1, r1, 3, st, 0, GACT_NONE, W_BOTH, W_BOTH);
-                bn(P + ".norm1", r1, a1, -1, GACT_RELU, W_BOTH);
+                bn(P + ".norm1", r1, a1, -1, GACT_RELU, W_BOTH, fz);
                 conv(P + ".conv2", a1, -1, r2, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH);
                 if (st != 1) {
                     const int rd = tensor(P + ".rd", N2, ho, wo, C, true), d = tensor(P + ".d", N2, ho, wo, C, true);
                     // module (= adapted-parameter) order inside the block: norm1, norm2, norm3 (encoder2d.py:33-37)
-                    bn(P + ".norm2", r2, out, d, GACT_RELU, W_BOTH).act_first = true;
+                    bn(P + ".norm2", r2, out, d, GACT_RELU, W_BOTH, fz).act_first = true;
                     Op bn2 = ops.back(); ops.pop_back();
                     conv(P + ".downsample.0", cur, -1, rd, 1, st, 0, GACT_NONE, W_BOTH, W_BOTH);
-                    bn(P + ".norm3", rd, d, -1, GACT_NONE, W_BOTH);
+                    bn(P + ".norm3", rd, d, -1, GACT_NONE, W_BOTH, fz);
                     ops.push_back(bn2);
                     if (bn2.fused_from >= 0) ops[bn2.fused_from].stat_to = (int)ops.size() - 1;
                 } else {
-                    bn(P + ".norm2", r2, out, cur, GACT_RELU, W_BOTH).act_first = true;
+                    bn(P + ".norm2", r2, out, cur, GACT_RELU, W_BOTH, fz).act_first = true;
                 }
                 cur = out; hh = ho; ww = wo;
             }
-        const int f16 = tensor("enc2d.out", N2, h4, w4, 16, true);
-        conv("enc2d.conv2", cur, -1, f16, 1, 1, 0, GACT_NONE, W_BOTH, W_BOTH);
         t_feat2d = tensor("feat2d", N2, h4, w4, 16, true);
-        if (!meta2) {
+        const int f16 = plain ? t_feat2d : tensor("enc2d.out", N2, h4, w4, 16, true);     // without the meta layer enc2d.conv2 feeds the fusion itself
+        conv("enc2d.conv2", cur, -1, f16, 1, 1, 0, GACT_NONE, W_BOTH, W_BOTH);
+        if (!plain && !meta2) {
             Op& m = conv("conv1_rgb_meta", f16, -1, t_feat2d, 3, 1, 0, GACT_NONE, W_BOTH, W_BOTH); m.ad_w = ad_mw; m.ad_b = ad_mb;
-        } else {
+        } else if (!plain) {
             // both passes, batch statistics per pass in train and eval mode; enc2d.out receives the data gradient of the first conv and the
             // residual's (Encoder2D's BatchNorm2d upstream are adapted)
             const int mh = tensor(MP + ".h", N2, h4, w4, 64, true), ma = tensor(MP + ".a", N2, h4, w4, 64, true), mr = tensor(MP + ".r", N2, h4, w4, 16, true);
@@ -175,11 +183,11 @@ struct costdc_engine : GNet {
         for (int i = 1; i < 4; ++i) {           // Down: MaxPool3d(2) + DoubleConv(in, out, mid = in)
             const int src = xl[i - 1], C = f[i - 1], per = N * D[i];
             char nm[64]; snprintf(nm, sizeof(nm), "unet3d.down%d", i);
-            const int pooled = tensor(std::string(nm) + ".pool", 2 * per, hs[i], ws[i], C, true, per);
+            const int pooled = tensor(std::string(nm) + ".pool", P2 * per, hs[i], ws[i], C, true, per);
             const int Hi = hs[i - 1], Wi = ws[i - 1];
             const int oi = func(nullptr, nullptr, src);
             ops[oi].ffwd = [this, src, pooled, Hi, Wi, C](bool train, hipStream_t s) {
-                const long items = (long)(train ? 2 : 1) * T[pooled].per;
+                const long items = (long)passes(W_BOTH, train) * T[pooled].per;
                 return cd_launch_pool_fwd(T[src].p, T[pooled].p, items, Hi, Wi, C, s) ? fail("max-pool failed", -5) : 0;
             };
             ops[oi].fbwd = [this, src, pooled, Hi, Wi, C, oi](hipStream_t s) {
@@ -193,11 +201,11 @@ struct costdc_engine : GNet {
         for (int i = 2; i >= 0; --i) {          // Up: nearest interpolate to the skip's size, cat([skip, up]), DoubleConv(in, out, mid = out)
             const int skip = xl[i], C = T[x].C, per = N * D[i];
             char nm[64]; snprintf(nm, sizeof(nm), "unet3d.up%d", 4 - i);
-            const int up = tensor(std::string(nm) + ".up", 2 * per, hs[i], ws[i], C, true, per);
+            const int up = tensor(std::string(nm) + ".up", P2 * per, hs[i], ws[i], C, true, per);
             const int Di = D[xi], Hi = hs[xi], Wi = ws[xi], Do = D[i], Ho = hs[i], Wo = ws[i], xs = x;
             const int oi = func(nullptr, nullptr, xs);
             ops[oi].ffwd = [this, xs, up, Di, Hi, Wi, Do, Ho, Wo, C](bool train, hipStream_t s) {
-                return cd_launch_up_fwd(T[xs].p, T[up].p, (long)(train ? 2 : 1) * N, Di, Hi, Wi, Do, Ho, Wo, C, s) ? fail("upsampling failed", -5) : 0;
+                return cd_launch_up_fwd(T[xs].p, T[up].p, (long)passes(W_BOTH, train) * N, Di, Hi, Wi, Do, Ho, Wo, C, s) ? fail("upsampling failed", -5) : 0;
             };
             ops[oi].fbwd = [this, xs, up, Di, Hi, Wi, Do, Ho, Wo, C, oi](hipStream_t s) {
                 return cd_launch_up_bwd(T[up].g, T[xs].g, (long)N, Di, Hi, Wi, Do, Ho, Wo, C, ops[oi].first_x[0] ? 0 : 1, s) ? fail("upsampling gradient failed", -5) : 0;
@@ -210,6 +218,13 @@ struct costdc_engine : GNet {
         conv("unet3d.classif0", x, -1, t_cost, 1, 1, 0, GACT_NONE, W_GRAD, W_GRAD);
         idx_regress = (int)ops.size();
         func([this](bool, hipStream_t s) { return regress_fwd(s); }, [this](hipStream_t s) { return regress_bwd(s); }, t_cost);
+        if (plain) {                                             // `_forward` has no heads: the loss gradient reaches the depth alone
+            plan_backward({});
+            if (meta_only) plan_eval_affine();
+            finish_build();
+            alloc_common(1, 16, 16);                             // no convolution has a weight gradient: the smallest partial buffer
+            return;
+        }
         // heads (CD:243-251, :463-465): emb = pred(proj(rows of the proxy pass)), ref = proj_t(rows of the real pass)
         t_rows = tensor("rows", N, fh, fw, 80 * fD, true);
         t_rows_p = tensor("rows_proxy", N, fh, fw, 80 * fD, false);
@@ -246,13 +261,15 @@ struct costdc_engine : GNet {
         t_ref = mlp("proj_t", t_rows, true); tid["ref"] = t_ref;
         plan_backward({t_ref});
         plan_head_affine(enc2d_ops_end);                       // stage-2 head trainer: the BatchNorm2d of that prefix (head_features)
-        // ---- remaining workspace ----
+        finish_build();
+        alloc_common((long)N * h4 * w4, 16, meta2 ? 64 : 16);      // weight-gradient partials of the widest adapted conv
+    }
+    void finish_build() {                                        // ---- remaining workspace ----
         const long P = (long)H * W;
         if (dual) { img_pad = falloc((size_t)N * 3 * P); sp_pad = falloc((size_t)N * P); }
         sp_clamp = falloc((size_t)N * P); pred_net = falloc((size_t)N * P); g_net = falloc((size_t)N * P);
         feat3d = falloc((size_t)N * 16 * h4 * w4 * 16); maskw = falloc((size_t)N * 16 * h4 * w4);
         build_sparse();
-        alloc_common((long)N * h4 * w4, 16, meta2 ? 64 : 16);      // weight-gradient partials of the widest adapted conv
     }
 
     // ---- sparse 3-D encoder (models/encoder3d.py) ---------------------------------------------------------------------------
@@ -301,8 +318,8 @@ struct costdc_engine : GNet {
                                        train ? &stat_sync : nullptr, b.st) ? fail("sparse batch-norm " + n + " failed", -5) : 0;
         if (bn_prepare == 2) train = false;      // the head trainer's SyncBatchNorm form: eval mode, from the loaded running statistics
         if (!train && (!b.rm || !b.rv)) return fail("running statistics of " + n + " not loaded", -3);
-        // train: the reference evaluates the sparse encoder once per pass on the same input (CD:216, :237): two updates
-        return cd_launch_sparse_bn(sp, f, res, level, b.C, b.g, b.b, b.rm, b.rv, b.nbt, train ? 1 : 0, 2, relu, out, s, &stat_sync) ? fail("sparse batch-norm " + n + " failed", -5) : 0;
+        // train: the reference evaluates the sparse encoder once per pass on the same input (CD:216, :237): two updates -- one in `_forward`
+        return cd_launch_sparse_bn(sp, f, res, level, b.C, b.g, b.b, b.rm, b.rv, b.nbt, train ? 1 : 0, passes(W_BOTH, true), relu, out, s, &stat_sync) ? fail("sparse batch-norm " + n + " failed", -5) : 0;
     }
     // sync_adapt: the same network with every BatchNorm's input and output kept, then its backward (BatchNorm gamma / beta gradients only)
     int sparse_encoder_adapt(bool train, hipStream_t s) {
@@ -390,7 +407,7 @@ struct costdc_engine : GNet {
     int fusion_fwd(bool train, hipStream_t s) {
         if (sp_inflight) { NCHK(hipStreamWaitEvent(s, ev_sp_done, 0)); sp_inflight = false; }
         else { const int rc = sparse_encoder(train, s); if (rc) return rc; }
-        return cd_launch_fusion_fwd(T[t_feat2d].p, feat3d, T[t_vol].p, maskw, N, train ? 2 : 1, h4, w4, s) ? fail("fusion failed", -5) : 0;
+        return cd_launch_fusion_fwd(T[t_feat2d].p, feat3d, T[t_vol].p, maskw, N, passes(W_BOTH, train), h4, w4, s) ? fail("fusion failed", -5) : 0;
     }
     int regress_fwd(hipStream_t s) {
         if (cd_launch_regress_fwd(T[t_cost].p, dual ? pred_net : depth, N, h4, w4, z_step, s)) return fail("depth regression failed", -5);
@@ -405,6 +422,8 @@ struct costdc_engine : GNet {
 
     // ---- weights that are not dense convolutions / affine BatchNorm parameters ---------------------------------------------------
     int load_extra(const std::string& name, const float* src, const int64_t* shape, int ndim, hipStream_t s) override {
+        // a stage-3 checkpoint holds the meta layer and the heads: `_forward` does not run them
+        if (plain && (name.compare(0, 15, "conv1_rgb_meta.") == 0 || name.compare(0, 4, "proj") == 0 || name.compare(0, 4, "pred") == 0)) return 0;
         auto ends = [&](const char* suf) { const size_t l = strlen(suf); return name.size() >= l && name.compare(name.size() - l, l, suf) == 0; };
         const size_t dot = name.rfind('.');
         const std::string base = dot == std::string::npos ? name : name.substr(0, dot), leaf = dot == std::string::npos ? "" : name.substr(dot + 1);
@@ -450,6 +469,7 @@ struct costdc_engine : GNet {
     int idx_regress = -1, idx_rows = -1;
     // stage-2 head trainer (ghead.hip): rows = the UNet3D bottleneck of the real pass / of the zero-image pass (CD:268-290); MLP(160, 512, 512)
     int head_spec(HeadSpec* hs) override {
+        if (plain) return fail(no_heads_why, -38);
         if (sync_adapt) return fail("the stage-2 head trainer runs on a handle without PTTA_SYNCBN_ADAPT", -38);
         if (dual) return fail("stage 2 runs on sizes divisible by 16", -38);
         hs->x_real = t_rows; hs->xw_real = W_GRAD; hs->x_proxy = t_rows_p; hs->xw_proxy = W_GRAD; hs->hidden = 512; hs->out = 512;
@@ -476,7 +496,7 @@ struct costdc_engine : GNet {
         // clamp (src/external_model_adapt.py:108) and cat([image | zeros, sparse]) staging; the reference normalises the image
         // before it pads, so padded pixels must stay zero: normalisation is applied to the caller's frame region only
         if (cd_launch_clamp(spp, sp_clamp, (long)N * H * W, hp.max_input_depth, s)) return fail("clamp failed", -5);
-        if (cd_launch_stage(img, sp_clamp, T[t_in].p, N, train ? 2 : 1, H, W, T[t_in].C, dual ? 0 : norm_on, norm_div, norm_mean, norm_std, s)) return fail("input staging failed", -5);
+        if (cd_launch_stage(img, sp_clamp, T[t_in].p, N, passes(W_BOTH, train), H, W, T[t_in].C, dual ? 0 : norm_on, norm_div, norm_mean, norm_std, s)) return fail("input staging failed", -5);
         sp_inflight = false;
         if (sp_async && !stat_sync.on()) {
             if (!sp_stream) {
@@ -525,6 +545,13 @@ GNet* costdc_create(int n, int h, int w, const ptta_hparams* hp, float max_depth
     e->use_graph = env.graph == 1 ? 1 : 0;
     e->sync_adapt = (flags & 1) ? 1 : 0;
     e->meta2 = (flags & 2) ? 1 : 0;
+    e->plain = (flags & 4) ? 1 : 0; e->one_pass = e->plain;
+    e->meta_only = (flags & 8) ? 1 : 0; e->eval_const_all = e->plain && e->meta_only;
+    if (e->plain) {
+        e->no_heads_why = "PTTA_COSTDC_PLAIN: this handle runs the network without the meta layer and has no heads (no stage-2 head trainer)";
+        e->one_rank_why = "PTTA_COSTDC_PLAIN: more than one rank is not offered (no statistics or gradient exchange)";
+        if (e->meta_only) e->no_train_why = "the source model (PTTA_COSTDC_PLAIN | PTTA_ADAPT_META_ONLY) adapts nothing: it has the eval forward only";
+    }
     e->build();
     if (e->oom || !e->step_dev) { delete e; *rc = -12; return nullptr; }
     if (e->upload_hparams(nullptr)) { delete e; *rc = -5; return nullptr; }

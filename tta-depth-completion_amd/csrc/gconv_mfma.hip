@@ -86,7 +86,9 @@ __global__ void gfrag_pack_kernel(const float* __restrict__ canon, long wld, lon
 // >= six_B (the proxy frames) skip the three extra products
 // ACTF: the affine epilogue's act_first form, relu(relu(fmaf(..)) + res) (GX3Args::aff_act_first): the inner ReLU in the register layout,
 // an instantiation of its own so that the others keep their code
-template <int KS, bool VERT, bool TIMING = false, bool SIX = false, bool ACTF = false>
+// ELU: the affine epilogue's ELU, v > 0 ? v : expm1f(v) behind the fmaf (gbn.hip gbn_act: CostDCNet's BatchNorm3d + ELU from constant statistics).
+// Its own instantiations for the reason `activate_cheap` states below: a run-time expm1f would be evaluated for every element of every launch
+template <int KS, bool VERT, bool TIMING = false, bool SIX = false, bool ACTF = false, bool ELU = false>
 __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p) {
     unsigned long long T0 = 0, ta = 0, tb = 0, tc = 0, td = 0, te = 0, tf = 0, tg = 0;
     unsigned long long dA = 0, dW = 0, dS = 0, dL = 0, dB = 0, dM = 0;
@@ -306,6 +308,7 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
                 float v = sig ? acc[rr][r] : acc[rr][r] + bias_w;
                 if (p.scale) v = fmaf(v, asc, ash);
                 if constexpr (ACTF) v = v > 0.f ? v : 0.f;
+                if constexpr (ELU) v = v > 0.f ? v : expm1f(v);         // (activate_cheap leaves GACT_ELU's value as it is)
                 if (!p.accumulate) {
                     v = (sig || p.res) ? v : activate_cheap(v);
                     if (yok && cok && x0 + px < W) { s1 += v; s2 += v * v; }
@@ -357,6 +360,7 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
             float v = acc[rr][r] + bias;
             if (p.scale) v = fmaf(v, asc, ash);
             if constexpr (ACTF) v = v > 0.f ? v : 0.f;
+            if constexpr (ELU) v = v > 0.f ? v : expm1f(v);             // (no residual, no accumulate: ptta_gx3_affine_ok; `activate` passes it on)
             if (p.accumulate) v += *dst;
             if (p.res) v += p.res[(((size_t)b * H + y) * W + x) * p.ld_res + co];
             v = activate(v);
@@ -963,6 +967,15 @@ int ptta_launch_gconv_x3(const GX3Args& a, int ks, hipStream_t s) {
         PTTA_CHECK_LAUNCH();
         return 0;
     }
+    if (a.act == GACT_ELU) {               // fmaf, then ELU: the 3-tap forms of CostDCNet's UNet3D (1x3x3 and the vertical 3x1x1), bf16x3 and bf16x6
+        if (ks != 3 || (a.six_B > 0 && !a.wl2)) return -22;
+        if (a.vert && a.six_B > 0) hipLaunchKernelGGL((gconv_x3_s1_kernel<3, true, false, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else if (a.vert) hipLaunchKernelGGL((gconv_x3_s1_kernel<3, true, false, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else if (a.six_B > 0) hipLaunchKernelGGL((gconv_x3_s1_kernel<3, false, false, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gconv_x3_s1_kernel<3, false, false, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        PTTA_CHECK_LAUNCH();
+        return 0;
+    }
     if (a.six_B > 0) {
         if (!a.wl2) return -22;
         if (ks == 3 && a.vert) hipLaunchKernelGGL((gconv_x3_s1_kernel<3, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
@@ -999,6 +1012,7 @@ int ptta_gconv_x3_strided_form(const GX3Args& a, int ks, int mode, int win, long
 int ptta_launch_gconv_x3_strided(const GX3Args& a, int ks, int mode, int hin, int win, hipStream_t s) {
     if ((a.C0 & 15) || (a.C1 & 15) || (a.ld0 & 3) || (a.ld1 & 3) || (ks != 1 && ks != 3) || (mode != 1 && mode != 2)) return -22;
     if (a.nchunks != (a.C0 + 31) / 32 + (a.C1 + 31) / 32 || !ptta_gx3_affine_ok(a)) return -22;
+    if (a.act == GACT_ELU) return -22;     // the ELU epilogue is the stride-1 kernel's (no strided convolution of an engine has one behind it)
     long nitems = 0;
     const int form = ptta_gconv_x3_strided_form(a, ks, mode, win, &nitems);
     const bool split = form == GX3_FORM_KSPLIT;

@@ -208,6 +208,15 @@ struct GNet {
     // per-channel affine (Op::st_eval, built once per load by prepare_eval_affines) that runs in the producing convolution's epilogue
     // (eval_bn_fused, option "eval_bn_fused") or as a separate gbn_apply; no statistics pass either way
     int meta_only = 0, eval_bn_fused = 1;
+    // a meta_only handle that never trains (CostDCNet's source model, include/ptta.h PTTA_COSTDC_PLAIN | PTTA_ADAPT_META_ONLY): the running
+    // statistics of its `tracked` BatchNorm are constants after a load too, so prepare_eval_affines builds their tables with the others and
+    // plan_affine pairs them with their convolutions -- the 3x1x1 (Op::rH) ones and ELU included -- and takes the act_first residual form
+    int eval_const_all = 0;
+    int eval_bn_fused_count() const {
+        int n = 0;
+        if (meta_only && eval_bn_fused) for (const Op& o : ops) n += o.kind == gnet::K_BN && o.aff_from >= 0;
+        return n;
+    }
     // one-pass training mode (include/ptta.h PTTA_META_NONE; the reference's `_forward`, nlspnmodel_adapt.py:792-848): a training forward is ONE
     // pass over the caller's frames -- no zero-image proxy pass, no heads.  A W_BOTH view holds `per` images in train mode too, BatchNorm and
     // the convolution epilogue's partial sums run one pass, the program holds no W_PROXY op and its tensors are allocated for `per` items.

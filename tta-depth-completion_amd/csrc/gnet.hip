@@ -81,15 +81,19 @@ int GNet::load(const char* name_c, const void* tensor_, const int64_t* shape, in
 void GNet::plan_affine(int end, bool stage2) {
     for (int i = 0; i < end && i < (int)ops.size(); ++i) {
         Op& b = ops[i];
-        if (b.kind != K_BN || b.tracked || b.train_only || b.rH > 0) continue;
-        if (!stage2 && (b.act_first || (b.res >= 0 && !b.res_relu))) continue;
-        if (b.act != GACT_NONE && b.act != GACT_RELU && b.act != GACT_LRELU) continue;
+        // all: a handle whose eval forward holds constant statistics everywhere (GNet::eval_const_all) -- tracked BatchNorm, the vertical
+        // 3x1x1 convolutions and ELU (the stride-1 3-tap kernels have that epilogue), and the act_first residual form of the stage-2 prefix
+        const bool all = !stage2 && eval_const_all;
+        if (b.kind != K_BN || b.train_only || ((b.tracked || b.rH > 0) && !all)) continue;
+        if (!stage2 && !all && (b.act_first || (b.res >= 0 && !b.res_relu))) continue;
+        if (b.act != GACT_NONE && b.act != GACT_RELU && b.act != GACT_LRELU && !(all && b.act == GACT_ELU && b.res < 0)) continue;
         if (!ptta_gbn_switches_ok(b.res >= 0, b.act, b.res_relu ? 1 : 0, b.act_first ? 1 : 0)) continue;
         int k = i - 1;
         while (k >= 0 && !(ops[k].kind == K_CONV && ops[k].y == b.x[0])) --k;
         if (k < 0) continue;
         const Op& c = ops[k];
-        if (!convs[c.wname].mf || c.act != GACT_NONE || c.yw != b.xw[0] || c.train_only || c.rH > 0 || convs[c.wname].vcol) continue;
+        if (!convs[c.wname].mf || c.act != GACT_NONE || c.yw != b.xw[0] || c.train_only || ((c.rH > 0 || convs[c.wname].vcol) && !all)) continue;
+        if (b.act == GACT_ELU && (c.k != 3 || c.stride != 1 || c.transposed)) continue;
         bool clean = true;
         for (int j = k + 1; j < i && clean; ++j) {
             const Op& m = ops[j];
@@ -105,7 +109,14 @@ void GNet::plan_affine(int end, bool stage2) {
 // the eval affine of every BatchNorm2d from its LOADED buffers (gbn_eval_affine_kernel: PTTA_GBN_EVAL's finalize); once per load()
 int GNet::prepare_eval_affines(hipStream_t s) {
     for (const Op& o : ops) {
-        if (o.kind != K_BN || o.tracked || o.train_only || o.st_eval_valid) continue;
+        if (o.kind != K_BN || (o.tracked && !eval_const_all) || o.train_only || o.st_eval_valid) continue;
+        if (o.tracked) {                         // bound buffers that nothing on this handle ever moves
+            if (!o.rm || !o.rv)
+                return fail(o.bname + (o.rm ? ".running_var" : ".running_mean") + " not loaded: this handle's eval forward normalises with the loaded running statistics (ptta_load_weights)", -3);
+            if (ptta_launch_gbn_eval_affine(bn_gamma(o), bn_beta(o), o.rm, o.rv, BN_EPS, T[o.x[0]].C, o.st_eval, s)) return fail("batch-norm " + o.bname + " (eval affine) launch failed", -5);
+            o.st_eval_valid = true;
+            continue;
+        }
         if (!o.has_rm || !o.has_rv)
             return fail(o.bname + (o.has_rm ? ".running_var" : ".running_mean") + " not loaded: this handle's eval forward normalises with the loaded running statistics (ptta_load_weights)", -3);
         if (ptta_launch_gbn_eval_affine(bn_gamma(o), bn_beta(o), o.rm_own, o.rv_own, BN_EPS, T[o.x[0]].C, o.st_eval, s)) return fail("batch-norm " + o.bname + " (eval affine) launch failed", -5);
@@ -223,6 +234,8 @@ int GNet::run_bn_fwd(const Op& o, bool train, hipStream_t s) {
             if (ptta_launch_gbn_eval_affine(bn_gamma(o), bn_beta(o), o.rm, o.rv, BN_EPS, x.C, o.st_eval, s)) return fail("batch-norm " + o.bname + " (eval) launch failed", -5);
             o.st_eval_valid = true;
         }
+        // the source model's BatchNorm3d + ELU in its convolution's epilogue (eval_const_all; the table came from prepare_eval_affines)
+        if (meta_only && !train && eval_bn_fused && o.aff_from >= 0) return run_conv_fwd(ops[o.aff_from], false, s, &o);
         if (ptta_launch_gbn_apply(x, res, y, 1, o.act, o.st_eval, o.res_relu ? 1 : 0, s, o.act_first ? 1 : 0))
             return fail("batch-norm " + o.bname + " (eval) launch failed", -5);
         return 0;

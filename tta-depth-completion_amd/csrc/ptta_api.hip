@@ -53,8 +53,16 @@ int ptta_create(ptta_handle* out, int backbone_id, int meta_mode, int n, int hei
         if ((dtype & 0xff) == PTTA_DTYPE_MIXED) return create_refused("PTTA_META_NONE with PTTA_DTYPE_MIXED: no bound has been measured for it");
         if (meta_mode & PTTA_NLSPN_SYNCBN_ADAPT) return create_refused("PTTA_META_NONE with PTTA_NLSPN_SYNCBN_ADAPT: there are no heads to append to the adapted list");
     }
+    // CostDCNet without the meta layer (include/ptta.h PTTA_COSTDC_PLAIN): `_forward` in fp32 on one rank -- the BatchNorm-adaptation baseline, or
+    // with PTTA_ADAPT_META_ONLY the source model; refused before anything is allocated
+    if (meta_mode & PTTA_COSTDC_PLAIN) {
+        if (backbone_id != PTTA_BACKBONE_COSTDCNET) return create_refused("PTTA_COSTDC_PLAIN: the flag belongs to the CostDCNet backbone (NLSPN has PTTA_META_NONE)");
+        if ((meta_mode & 0xff) != PTTA_META_1LAYER) return create_refused("PTTA_COSTDC_PLAIN with PTTA_META_2LAYERS or PTTA_META_NONE: the flag itself takes the meta layer out, its base mode is PTTA_META_1LAYER");
+        if (meta_mode & PTTA_SYNCBN_ADAPT) return create_refused("PTTA_COSTDC_PLAIN with PTTA_SYNCBN_ADAPT: there are no heads to append to the adapted list");
+        if ((dtype & 0xff) == PTTA_DTYPE_MIXED) return create_refused("PTTA_COSTDC_PLAIN with PTTA_DTYPE_MIXED: no bound has been measured for it");
+    }
     // the meta-only adapted list is built for NLSPN's 1layer meta conv in fp32 (include/ptta.h PTTA_ADAPT_META_ONLY); refused before anything is allocated
-    if (meta_mode & PTTA_ADAPT_META_ONLY) {
+    if ((meta_mode & PTTA_ADAPT_META_ONLY) && !(meta_mode & PTTA_COSTDC_PLAIN)) {
         if (backbone_id != PTTA_BACKBONE_NLSPN) return create_refused("PTTA_ADAPT_META_ONLY: only the NLSPN adapter has adapt_mode 'meta'");
         if ((meta_mode & 0xff) == PTTA_META_2LAYERS) return create_refused("PTTA_ADAPT_META_ONLY with PTTA_META_2LAYERS: the block's own BatchNorm2d under 'meta' is not built");
         if ((dtype & 0xff) == PTTA_DTYPE_MIXED) return create_refused("PTTA_ADAPT_META_ONLY with PTTA_DTYPE_MIXED: no bound has been measured for it");
@@ -83,11 +91,13 @@ int ptta_create(ptta_handle* out, int backbone_id, int meta_mode, int n, int hei
         // 320x400, with hi + lo weights in them still 1.1e-3 / 1.2e-3, with single-MFMA proxy frames alone 8.9e-4 at 320x400, for 2 - 3 % of
         // the step: profiles/r06_nlspn_costdcnet_mixed.txt -- its argmax over the cost volume amplifies any change of the update)
         // 2layers: the Res_Conv(16, 64) block (costdc_api.hip), fp32 only, not with PTTA_SYNCBN_ADAPT
-        const int meta = meta_mode & ~PTTA_SYNCBN_ADAPT;
+        const int plain = (meta_mode & PTTA_COSTDC_PLAIN) ? 1 : 0;         // (PTTA_ADAPT_META_ONLY without it was refused above)
+        const int meta = meta_mode & ~(PTTA_SYNCBN_ADAPT | (plain ? (PTTA_COSTDC_PLAIN | PTTA_ADAPT_META_ONLY) : 0));
         if ((meta != PTTA_META_1LAYER && meta != PTTA_META_2LAYERS) || dtype != PTTA_DTYPE_F32 || !hp || gmix) return -38;
         if (meta == PTTA_META_2LAYERS && (meta_mode & PTTA_SYNCBN_ADAPT)) return -38;
         int rc = 0;
-        GNet* e = costdc_create(n, height, width, hp, hp->max_predict_depth, ((meta_mode & PTTA_SYNCBN_ADAPT) ? 1 : 0) | (meta == PTTA_META_2LAYERS ? 2 : 0), &rc);
+        GNet* e = costdc_create(n, height, width, hp, hp->max_predict_depth, ((meta_mode & PTTA_SYNCBN_ADAPT) ? 1 : 0) | (meta == PTTA_META_2LAYERS ? 2 : 0) |
+                                (plain ? 4 : 0) | ((plain && (meta_mode & PTTA_ADAPT_META_ONLY)) ? 8 : 0), &rc);
         return wrap_gnet(out, e, rc, gmix, n, height, width, hp);
     }
     if (backbone_id != PTTA_BACKBONE_MSG_CHN || (meta_mode != PTTA_META_1LAYER && meta_mode != PTTA_META_2LAYERS)) return -38;
@@ -458,7 +468,9 @@ int ptta_set_option(ptta_handle c, const char* key, int value) {
     if (!c || !key) return -1;
     const std::string k(key);
     if (k == "graph") return ptta_set_graph(c, value);
-    if (k == "eval_bn_fused") {                    // meta-only NLSPN handles: the eval BatchNorm2d in the convolution epilogue (1) or as its own launch (0)
+    if (k == "eval_bn_fused_count") return c->nl ? (c->err.clear(), c->nl->fail("ptta_set_option: 'eval_bn_fused_count' is read-only", -22))
+                                                 : c->fail("ptta_set_option: 'eval_bn_fused_count' is read-only", -22);
+    if (k == "eval_bn_fused") {                    // meta-only handles (NLSPN, CostDCNet's source model): the eval BatchNorm in the convolution epilogue (1) or as its own launch (0)
         if (!c->nl || !c->nl->meta_only) return c->nl ? (c->err.clear(), c->nl->fail("ptta_set_option: 'eval_bn_fused' belongs to PTTA_ADAPT_META_ONLY handles", -38))
                                                       : c->fail("ptta_set_option: 'eval_bn_fused' belongs to PTTA_ADAPT_META_ONLY handles", -38);
         c->err.clear();
@@ -501,6 +513,8 @@ int ptta_get_option(ptta_handle c, const char* key, int* value) {
     // without the caller's stream (the second stream is created on first use)
     if (k == "thru_active") { *value = c->nl ? 0 : (c->thru && c->cos_grad_fused && heads_v2_on(c) && c->use_aux); return 0; }
     if (k == "eval_bn_fused") { if (!c->nl || !c->nl->meta_only) return -38; *value = c->nl->eval_bn_fused; return 0; }
+    // read-only: how many BatchNorm of the eval forward ride in a convolution epilogue as configured now (0 with "eval_bn_fused" at 0)
+    if (k == "eval_bn_fused_count") { if (!c->nl || !c->nl->meta_only) return -38; *value = c->nl->eval_bn_fused_count(); return 0; }
     if (k == "head_bn_fused" || k == "head_bn_fused_count") {
         if (!c->nl) return -38;
         *value = k == "head_bn_fused" ? c->nl->head_bn_fused : c->nl->head_bn_fused_count();

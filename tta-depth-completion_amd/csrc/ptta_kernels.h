@@ -390,12 +390,15 @@ struct GX3Args {
     // the two other residual forms of gbn_apply_kernel behind the affine (the stage-2 head trainer's frozen BatchNorm2d):
     //   aff_act_first: y = relu(relu(fmaf(..)) + res)   -- CostDCNet's ResBlock (Op::act_first); act = GACT_RELU, instantiations of their own
     //   aff_res_plain: y = fmaf(..) + res                -- the 2layers block's last BatchNorm2d (Op::res_relu = false); act = GACT_NONE
+    // act = GACT_ELU exists behind the affine only, without a residual (CostDCNet's BatchNorm3d + ELU; stride-1 3-tap kernels, vert or not)
     int aff_act_first = 0, aff_res_plain = 0;
 };
-// the affine epilogue's own argument rules, checked by both launchers before their launch: what ptta_gbn_switches_ok refuses is refused here
+// the affine epilogue's own argument rules, checked by both launchers before their launch: what ptta_gbn_switches_ok refuses is refused here.
+// It also guards the one non-affine case: a plain launch with act = GACT_ELU is refused, because ELU exists in the affine epilogue only
 inline bool ptta_gx3_affine_ok(const GX3Args& a) {
-    if (!a.scale && !a.shift && !a.res && !a.aff_act_first && !a.aff_res_plain) return true;
-    if (!a.scale || !a.shift || a.accumulate || a.stat_part || (a.act != GACT_NONE && a.act != GACT_RELU && a.act != GACT_LRELU)) return false;
+    if (!a.scale && !a.shift && !a.res && !a.aff_act_first && !a.aff_res_plain) return a.act != GACT_ELU;
+    if (!a.scale || !a.shift || a.accumulate || a.stat_part) return false;
+    if (a.act != GACT_NONE && a.act != GACT_RELU && a.act != GACT_LRELU && !(a.act == GACT_ELU && !a.res)) return false;
     if (a.aff_act_first && (a.aff_res_plain || !a.res || a.act != GACT_RELU || a.vert)) return false;
     if (a.aff_res_plain && (!a.res || a.act != GACT_NONE)) return false;
     return !a.res || a.ld_res >= a.Cy;

@@ -256,18 +256,21 @@ static int op_gconv(const float* x0, int c0, int ld0, const float* x1, int c1, i
     if (affine) {
         const int cm = geom == PTTA_GCONV_S1 ? 7 : 15;          // channel counts the matrix-core forms take (ptta_launch_gconv_x3 / _strided)
         if (!scale || !shift || (((size_t)scale | (size_t)shift) & 15) || (res != nullptr) != (ld_res != 0) || (res && ld_res < co) ||
-            impl != 0 || accumulate || stat_npass || six_b < 0 || six_b > b || (flags & PTTA_GCONV_DGRAD) || (act != GACT_NONE && act != GACT_RELU && act != GACT_LRELU) ||
+            impl != 0 || accumulate || stat_npass || six_b < 0 || six_b > b || (flags & PTTA_GCONV_DGRAD) ||
+            (act != GACT_NONE && act != GACT_RELU && act != GACT_LRELU && act != GACT_ELU) ||
             c0 < 1 || c1 < 0 || (c0 & cm) || (c1 & cm)) return -22;
         // the residual forms, as ptta_gbn_switches_ok has them: act_first takes a residual and ReLU, the plain residual no activation
         const bool af = flags & PTTA_GCONV_AFF_ACT_FIRST, rp = flags & PTTA_GCONV_AFF_RES_PLAIN;
         if ((af && rp) || (af && (!res || act != GACT_RELU || (flags & PTTA_GCONV_VERT))) || (rp && (!res || act != GACT_NONE))) return -22;
         // the transposed geometry has the plain bf16x3 epilogue only (ptta_launch_gconv_x3_strided)
         if (geom == PTTA_GCONV_T2 && (af || six_b > 0)) return -22;
+        // ELU: behind the stride-1 3-tap kernels only (square or PTTA_GCONV_VERT), never with a residual
+        if (act == GACT_ELU && (geom != PTTA_GCONV_S1 || k != 3 || res || af || rp)) return -22;
     } else if (flags & (PTTA_GCONV_AFF_ACT_FIRST | PTTA_GCONV_AFF_RES_PLAIN)) return -22;
     const bool vert = flags & PTTA_GCONV_VERT, dgrad = flags & PTTA_GCONV_DGRAD;
     if (!x0 || !weight || !y || b < 1 || hin < 1 || win < 1 || hout < 1 || wout < 1 || c0 < 1 || c1 < 0 || co < 1 || ld0 < c0 || ldy < co ||
         (c1 > 0) != (x1 != nullptr) || (c1 > 0 && ld1 < c1) || (k != 1 && k != 3) || geom < PTTA_GCONV_S1 || geom > PTTA_GCONV_T2 ||
-        act < GACT_NONE || act > GACT_SIGMOID || impl < 0 || impl > 1 || (flags & ~31) || six_b < 0 || six_b > b || x1_from_b < 0 ||
+        act < GACT_NONE || act > (affine ? GACT_ELU : GACT_SIGMOID) || impl < 0 || impl > 1 || (flags & ~31) || six_b < 0 || six_b > b || x1_from_b < 0 ||
         stat_npass < 0 || stat_npass > 2 || (accumulate & ~1)) return -22;
     if (vert && (k != 3 || geom != PTTA_GCONV_S1)) return -22;
     if (dgrad && (c1 > 0 || six_b > 0)) return -22;

@@ -53,6 +53,21 @@ def _unique(names):
     return out
 
 
+class _PlainForwardFn(torch.autograd.Function):
+    """depth = `_forward`(image, sparse) in training mode on the baseline engine; backward -> gradients of the 30 BatchNorm2d tensors."""
+
+    @staticmethod
+    def forward(ctx, eng, image, sparse, *adapted):
+        depth, _, _ = eng.forward_train(image, sparse)
+        ctx.eng = eng
+        ctx.params = dict(zip(eng.adapted, adapted))
+        return depth
+
+    @staticmethod
+    def backward(ctx, g_depth):
+        return (None, None, None) + tuple(ctx.eng.backward_all(g_depth, None, ctx.params))
+
+
 class CostDCNetModel_Adapt(MsgChnModel_Adapt):
     """Counterpart of src/costdcnet_model_adapt.py:31-556."""
 
@@ -73,6 +88,8 @@ class CostDCNetModel_Adapt(MsgChnModel_Adapt):
         self._opt_state = {}
         self._adam_t = 0
         self.sync_bn = False
+        self.stats_dropped = False        # adapt_parameters('meta_bn') ran: Encoder2D's BatchNorm2d lost their running statistics
+        self._weights_version = 0         # counts the ProxyTTA training calls: see _plain_engine
         self.hparams = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, w_sparse_depth=1.0, w_smoothness=1.0, w_cos=1.0)
         self.total_time = self.train_time = self.eval_time = 0.0
         self.to(device)
@@ -105,6 +122,20 @@ class CostDCNetModel_Adapt(MsgChnModel_Adapt):
     def adapt_parameters(self, mode=None):
         if mode != 'meta_bn':
             raise NotImplementedError("adapt_mode %r: only 'meta_bn' (the CostDCNet scripts' mode) is on the accelerated path" % mode)
+        if self.prepare_mode is None:
+            # the BatchNorm-adaptation baseline (src/costdcnet_model_adapt.py:357-378 on a model whose head was never prepared): no parameter is
+            # called 'meta' yet, so the list is gamma / beta of Encoder2D's 15 BatchNorm2d (30 tensors); forward / step / compute_loss then
+            # run on the engine without the meta layer (include/ptta.h PTTA_COSTDC_PLAIN)
+            if self.sync_bn:
+                raise NotImplementedError('the BatchNorm-adaptation baseline runs on one rank (no SyncBatchNorm form)')
+            keys = [k for k, _ in synth.costdcnet_keys() if not k.startswith(('proj', 'pred', 'conv1_rgb_meta'))]
+            self.adapted_listed = costdcnet_adapted_names(keys)
+            self.adapted = list(self.adapted_listed)
+            self._never_stepped = set()
+            self._clear_engines()
+        elif not self.stats_dropped:
+            self._drop_plain_engines()             # a source engine made so far normalised with the statistics this call drops
+        self.stats_dropped = True
         params = dict(self.model.named_parameters())
         # the DDP list names four tensors twice: torch.optim.Adam then steps them twice per step(), like the reference's.  The reference
         # pins torch 1.10.1 (README.md:74: one entry at a time, two complete consecutive updates -- what step() does on device); with
@@ -145,6 +176,8 @@ class CostDCNetModel_Adapt(MsgChnModel_Adapt):
         eng = self._engines.get(key)
         if eng is None:
             if self.prepare_mode is None:
+                if self.stats_dropped:             # the baseline model: its only engine is the one without the meta layer
+                    return self._plain_engine(image)
                 raise RuntimeError('_prepare_head(mode) must be called before forward (tta_main.py:322)')
             eng = Engine(n, h, w, backbone='costdcnet', max_input_depth=self.max_input_depth, max_predict_depth=self.max_depth,
                          syncbn_adapted=self.sync_bn, meta=self.meta, **self.hparams)
@@ -164,12 +197,86 @@ class CostDCNetModel_Adapt(MsgChnModel_Adapt):
             self._engines[key] = eng
         return eng
 
+    def _plain_engine(self, image):
+        """The engine of `_forward`, the network without the meta layer (include/ptta.h PTTA_COSTDC_PLAIN): the baseline kind once
+        adapt_parameters('meta_bn') dropped Encoder2D's running statistics (batch statistics there, its gamma / beta bound to this model's
+        parameters), the source kind before (every BatchNorm from the loaded running statistics, eval forward only).  One per shape, beside
+        the ProxyTTA engines; the meta layer and the heads of a prepared model are not part of it.
+        The source kind COPIES gamma / beta and Encoder2D's statistics and builds its BatchNorm tables once per load, and either kind reads
+        BatchNorm3d / sparse buffers that a ProxyTTA engine of the same model updates in place: a plain engine that is older than the last
+        ProxyTTA training call (`_weights_version`) loads the model's state again before it runs.  An optimizer outside the library
+        (forward -> loss.backward() -> torch.optim.Adam.step) writes gamma / beta after that call: torch counts every in-place write of a
+        tensor, so the stamp an engine carries (`_plain_stamp`) holds those counts too, and a 'pretrain' call on either side of
+        optimizer.step() sees the parameters as they are."""
+        if self.sync_bn:
+            raise NotImplementedError("the network without the meta layer runs on one rank (no SyncBatchNorm form of loss_type 'pretrain')")
+        n, _, h, w = image.shape
+        key = ('plain', n, h, w)
+        eng = self._engines.get(key)
+        state = lambda: {k: v for k, v in self.model.state_dict().items() if not k.startswith(('proj', 'pred', 'conv1_rgb_meta'))}
+        if eng is None:
+            baseline = self.stats_dropped
+            eng = Engine(n, h, w, backbone='costdcnet', max_input_depth=self.max_input_depth, max_predict_depth=self.max_depth,
+                         meta='plain', adapt_mode='meta_bn' if baseline else 'meta', **self.hparams)
+            want = [k for k in self.adapted if k.startswith('enc2d.')] if baseline else []
+            assert eng.adapted == want and all(eng.adapted_repeat[k] == 1 for k in want), 'adapted parameter list drifted from the library'
+            eng.load_state_dict(state())
+            params = dict(self.model.named_parameters())
+            for name in eng.adapted:
+                p = params[name]
+                st = self._opt_state.setdefault(name, {'exp_avg': torch.zeros_like(p.data), 'exp_avg_sq': torch.zeros_like(p.data)})
+                eng.bind_adapted(name, p.data, st['exp_avg'], st['exp_avg_sq'])
+            if getattr(self, '_image_norm', None) is not None:
+                eng.set_image_norm(self._image_norm)
+            eng._t = 0
+            eng._version = self._plain_stamp()
+            self._engines[key] = eng
+        elif eng._version != self._plain_stamp():
+            eng.load_state_dict(state())
+            eng._version = self._plain_stamp()
+        return eng
+
+    def _plain_stamp(self):
+        """What a plain engine's copy of this model was taken at: the ProxyTTA training calls so far (they move buffers and, in the fused step,
+        parameters through the library) and torch's write counts of Encoder2D's parameters (an optimizer's in-place updates)."""
+        return (self._weights_version, sum(p._version for k, p in self.model.named_parameters() if k.startswith('enc2d.')))
+
+    def _drop_plain_engines(self):
+        for key in [k for k in self._engines if k[0] == 'plain']:
+            self._engines.pop(key).close()
+
+    def step(self, image, sparse_depth, validity_map=None, loss_image=None, want_depth=False, next_frame=None):
+        if self.prepare_mode is not None:
+            self._weights_version += 1             # a ProxyTTA step moves what a plain engine of this model copied or tabulated
+        return super().step(image, sparse_depth, validity_map, loss_image, want_depth, next_frame)
+
+    def _forward_plain(self, image, sparse_depth, loss_type):
+        """`_forward` (CostDCNet_adapt.py:177-205).  Eval: the depth.  Training with 'bn' in the string: (depth, None, None) with autograd edges
+        to the 30 BatchNorm2d tensors of the baseline.  Training without 'bn': the reference returns a tensor with autograd into EVERY
+        parameter, which is not on the accelerated path."""
+        if self.training:
+            if 'bn' not in loss_type:
+                raise NotImplementedError("loss_type %r in training mode: autograd into every parameter is not on the accelerated path "
+                                          "('bn' in the string: the BatchNorm-adaptation baseline)" % loss_type)
+            if not self.stats_dropped or self.prepare_mode is not None:
+                raise RuntimeError("loss_type %r in training mode follows adapt_parameters('meta_bn') on a model whose head was never prepared "
+                                   "(the BatchNorm-adaptation baseline)" % loss_type)
+            eng = self._plain_engine(image)
+            params = dict(self.model.named_parameters())
+            depth = self._timed(lambda: _PlainForwardFn.apply(eng, image, sparse_depth, *[params[k] for k in eng.adapted]), loss_type)
+            return depth, None, None
+        with torch.no_grad():
+            return self._timed(lambda: self._plain_engine(image).forward_eval(image, sparse_depth), loss_type)
+
     def forward(self, image, sparse_depth, intrinsics=None, crop_mask=None, loss_type='pretrain'):
+        if 'pretrain' in loss_type:                # the first test of CostDCNet.forward (CostDCNet_adapt.py:44-54), on a prepared model too
+            return self._forward_plain(image, sparse_depth, loss_type)
         if 'head' in loss_type and 'init_meta' not in loss_type and loss_type != 'prepare':       # stage 2 (src/head_main.py:464-468)
             if not self.training:
                 raise NotImplementedError('the head forward is a training-mode call (head_main.py:441)')
             return self.head_forward(image, sparse_depth, loss_type)
         if self.training and 'adapt' in loss_type:
+            self._weights_version += 1
             params = dict(self.model.named_parameters())
             return self._timed(lambda: _ForwardFn.apply(self, image, sparse_depth, *[params[k] for k in self.adapted]), loss_type)
         with torch.no_grad():

@@ -67,8 +67,11 @@ class Engine:
         self.adapt_mode = adapt_mode
         # meta 'none' (NLSPN): the network without the meta layer, one pass, no heads (include/ptta.h PTTA_META_NONE) -- with adapt_mode 'meta_bn'
         # the BatchNorm-adaptation baseline (86 adapted tensors), with 'meta' / 'meta_fix' the source model (nothing adapts, eval forward only)
-        if meta not in ('1layer', '2layers', 'none'):
-            raise ValueError("meta must be '1layer', '2layers' or 'none'")
+        # meta 'plain' (CostDCNet): the same for that backbone (include/ptta.h PTTA_COSTDC_PLAIN): 30 adapted tensors / the source model
+        if meta not in ('1layer', '2layers', 'none', 'plain'):
+            raise ValueError("meta must be '1layer', '2layers', 'none' (NLSPN) or 'plain' (CostDCNet)")
+        if meta == 'plain' and backbone != 'costdcnet':
+            raise ValueError("meta 'plain' belongs to the CostDCNet backbone (NLSPN has 'none')")
         self.emb_dim = 1024 if backbone == 'nlspn' else 512
         if backbone == 'costdcnet' and not max_predict_depth:
             raise ValueError('CostDCNet needs max_predict_depth (the far plane of its cost volume, ExternalModel_Adapt(max_predict_depth))')
@@ -88,6 +91,7 @@ class Engine:
                                   {'2layers': _lib.PTTA_META_2LAYERS, 'none': _lib.PTTA_META_NONE}.get(meta, _lib.PTTA_META_1LAYER) |
                                   (_lib.PTTA_NLSPN_LEGACY_OFFSET if (legacy_offset and backbone == 'nlspn') else 0) |
                                   (_lib.PTTA_SYNCBN_ADAPT if (syncbn_adapted and backbone in ('nlspn', 'costdcnet')) else 0) |
+                                  (_lib.PTTA_COSTDC_PLAIN if meta == 'plain' else 0) |
                                   (_lib.PTTA_ADAPT_META_ONLY if adapt_mode != 'meta_bn' else 0),
                                   self.n, self.h, self.w, code, byref(self.hp))
         if rc != 0:
@@ -180,7 +184,7 @@ class Engine:
         sparse = self._f32(sparse, (self.n, 1, self.h, self.w))
         depth = torch.empty((self.n, 1, self.h, self.w), device=image.device, dtype=torch.float32)
         emb = ref = None
-        if want_emb and self.meta != 'none':       # a handle without heads writes the depth only: (depth, None, None)
+        if want_emb and self.meta not in ('none', 'plain'):       # a handle without heads writes the depth only: (depth, None, None)
             emb = torch.empty((self.rows, self.emb_dim), device=image.device, dtype=torch.float32)
             ref = torch.empty_like(emb)
         self._chk(self.lib.ptta_forward_train(self.handle, ptr(image), ptr(sparse), ptr(depth), ptr(emb),
@@ -555,12 +559,17 @@ def op_gconv(x0, weight, y, x1=None, bias=None, k=3, geom='s1', act='none', accu
     return GCONV_FORMS[form.value], st
 
 
+GCONV_AFFINE_ACTS = dict(GCONV_ACTS, elu=4)      # ELU exists behind the affine only (CostDCNet's BatchNorm3d + ELU)
+
+
 def op_gconv_affine(x0, weight, y, scale, shift, x1=None, bias=None, res=None, ld_res=None, k=3, geom='s1', act='none', impl='mfma',
-                    accumulate=False, act_first=False, res_plain=False, six_b=0):
+                    accumulate=False, act_first=False, res_plain=False, six_b=0, vert=False, stat_npass=0):
     """Test hook: op_gconv with the eval-BatchNorm epilogue of NLSPN's meta-only mode and of the stage-2 head trainer (include/ptta.h
     ptta_op_gconv_affine): y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res]); act_first: relu(relu(fmaf(..)) + res); res_plain:
     fmaf(..) + res.  scale / shift [co] device tensors; res [b, hout, wout, co], possibly a channel slice of a wider tensor; ld_res
-    overrides the residual's pixel stride (the argument checks); six_b: the images below it in bf16x6.  Returns the strided launch form."""
+    overrides the residual's pixel stride (the argument checks); six_b: the images below it in bf16x6.  act 'elu' (stride 1, k = 3, no
+    residual): fmaf, then v > 0 ? v : expm1(v); vert: the three vertical taps of a 3x1x1 Conv3d, weight [co][ci][3][1].  stat_npass: only
+    for the argument checks (the epilogue has no fused statistics).  Returns the strided launch form."""
     lib = _lib.load()
 
     def view(t):
@@ -575,10 +584,12 @@ def op_gconv_affine(x0, weight, y, scale, shift, x1=None, bias=None, res=None, l
     py, co, ldy = view(y)
     pr, _, ldr = view(res) if res is not None else (None, 0, 0)
     form = c_int(-1)
+    stats = (ctypes.c_double * (stat_npass * 2 * co))() if stat_npass else None
     rc = lib.ptta_op_gconv_affine(p0, c0, ld0, p1, c1, ld1, ptr(weight.contiguous()), ptr(bias), py, co, ldy, b, hin, win, hout, wout, k,
-                                  GCONV_GEOMS[geom], GCONV_ACTS[act], int(bool(accumulate)), GCONV_IMPLS[impl],
-                                  (_lib.PTTA_GCONV_AFF_ACT_FIRST if act_first else 0) | (_lib.PTTA_GCONV_AFF_RES_PLAIN if res_plain else 0),
-                                  int(six_b), 1 << 30, 0, None,
+                                  GCONV_GEOMS[geom], GCONV_AFFINE_ACTS[act], int(bool(accumulate)), GCONV_IMPLS[impl],
+                                  (_lib.PTTA_GCONV_AFF_ACT_FIRST if act_first else 0) | (_lib.PTTA_GCONV_AFF_RES_PLAIN if res_plain else 0) |
+                                  (_lib.PTTA_GCONV_VERT if vert else 0),
+                                  int(six_b), 1 << 30, int(stat_npass), stats,
                                   byref(form), ptr(scale), ptr(shift), pr, ldr if ld_res is None else int(ld_res), _stream())
     if rc != 0:
         raise RuntimeError('ptta_op_gconv_affine failed (%d)' % rc)
