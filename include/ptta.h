@@ -734,6 +734,81 @@ int ptta_op_cd_densify(ptta_cd_sparse* q, const float* in, float* out, int c, in
 #define PTTA_CD_ROWS_FWD 13
 #define PTTA_CD_ROWS_BWD 14
 int ptta_op_cd_dense(int op, const float* a, const float* b, float* out, float* out2, const int* d, const float* f, ptta_stream s);
+/* Test hooks: the MSG_CHN step's first-layer / prediction convolutions (csrc/conv_small.hip), resamplings (csrc/resample.hip) and loss
+ * (csrc/loss.hip) on caller-supplied fp32 device buffers, packed and launched through the launchers of csrc/ptta_kernels.h exactly as
+ * csrc/msgchn_forward.hip, msgchn_backward.hip and msgchn_step.hip launch them (tests/test_gpu_msgchn_elementwise.py).  All of them
+ * synchronise; -22 BEFORE any launch (and before any allocation) for arguments a kernel would index out of bounds or misalign with, -12 out
+ * of memory, -5 a HIP error.  dtype other than PTTA_DTYPE_F32: the 32-channel maps are converted to narrow (bf16) storage and back, as
+ * ptta_op_conv32 does; planar one-channel maps stay fp32 in both modes.
+ *
+ * ptta_op_conv_in: planar planes pl[0 .. cin) (each [nb][h][w], frame b % nb, optional normalisation (v / div - mean) / stdv of in-frame
+ * samples) -> 32-channel NHWC.  weight as the state dict holds it, [32][cin_total][3][3] from input channel cin_first on, or with
+ * transpose_flip the [1][32][3][3] weight of a 32 -> 1 convolution packed as its input gradient (cin 1).  Epilogue, each operand optional:
+ * bias [32]; up [up_nb][h/2][w/2][32] (bilinear x2, h and w even); ReLU mask as a float map mask [mask_nb][h][w][32] and / or sign-bit
+ * words mask_bits [mask_nb][h][w]; add1 [add1_nb][h][w][32] (goes into out_sum only).  out_raw / out_sum [b][h][w][32] (either may be NULL,
+ * not both; a NULL one is not written); a_bits [b][h][w]: the sign-bit words of out_raw for frames below a_bits_nb.  Frames from
+ * zero_from_b on see a zero input (the proxy pass).  max_blocks > 0 caps the grid.  *form_host: the kernel that ran -- 0 LDS-staged,
+ * 1 LDS-staged with mask, 2 the direct matrix-core form (taken with up or add1), 3 naive.  Refused: a narrow launch with a float mask and
+ * no bit words; bit words without a float mask in the direct and naive forms, or any mask there in a narrow launch (those kernels read the
+ * map); a_bits outside the fp32 LDS-staged forms (nothing else writes them). */
+typedef struct ptta_plane { const float* p; int nb; int norm; float div, mean, stdv; } ptta_plane;
+typedef struct ptta_conv_in_args {
+    int cin, cin_total, cin_first, transpose_flip, up_nb, mask_nb, add1_nb, a_bits_nb, zero_from_b, b, h, w, dtype, naive, max_blocks;
+    ptta_plane pl[3];
+    const float* weight; const float* bias; const float* up; const float* mask; const uint32_t* mask_bits; const float* add1;
+    float* out_raw; float* out_sum; uint32_t* a_bits;
+} ptta_conv_in_args;
+int ptta_op_conv_in(const ptta_conv_in_args* a, int* form_host, ptta_stream s);
+/* ptta_op_conv_out1: in [in_nb][h][w][32] (frame b % in_nb, ReLU on load with relu_in) -> out [b][h][w] = conv + bias[0] + add[b % add_nb]
+ * (bias, add may be NULL).  weight [1][32][3][3], or with from_conv_in the [32][src_cin_total][3][3] weight of a first layer packed as the
+ * input gradient with respect to its plane src_cin_index.  max_blocks > 0 caps the grid. */
+typedef struct ptta_conv_out1_args {
+    int in_nb, src_cin_total, src_cin_index, from_conv_in, add_nb, relu_in, dtype, b, h, w, max_blocks;
+    const float* in; const float* weight; const float* bias; const float* add; float* out;
+} ptta_conv_out1_args;
+int ptta_op_conv_out1(const ptta_conv_out1_args* a, ptta_stream s);
+/* ptta_op_prep: sparse [n][h][w] -> dclamp (clamped to [0, max_input_depth]; max_input_depth < 0: a copy), d12 [n][h/2][w/2] and d14
+ * [n][h/4][w/4] = avg_pool(d) / (avg_pool(d > 0) + 1e-4).  h, w multiples of 4 (else -22).
+ * ptta_op_up2_1ch: in [b][hin][win] -> out [b][2 hin][2 win], bilinear x2 with align_corners; ptta_op_up2t_1ch its transpose, gout
+ * [b][2 hin][2 win] -> gin [b][hin][win]; ptta_op_up2t_32 the transpose on 32-channel NHWC maps, gin = add + up2^T(gout) (add may be NULL). */
+int ptta_op_prep(const float* sparse, float max_input_depth, float* dclamp, float* d12, float* d14, int n, int h, int w, ptta_stream s);
+int ptta_op_up2_1ch(const float* in, float* out, int b, int hin, int win, ptta_stream s);
+int ptta_op_up2t_1ch(const float* gout, float* gin, int b, int hin, int win, ptta_stream s);
+int ptta_op_up2t_32(const float* gout_nhwc, const float* add_nhwc, float* gin_nhwc, int b, int hin, int win, int dtype, ptta_stream s);
+/* ptta_op_loss: the adaptation loss and its gradients, every launch form.  depth, sparse, validity (NULL: where(sparse > 0, 1, sparse))
+ * [n][h][w], image [n][3][h][w], emb / ref [r][d] (both or neither), the weights w_sd, w_sm, w_cos.  The workspace has
+ * the size the engine gives it (csrc/loss.hip) and starts NaN-filled.
+ *   fwd  PTTA_LOSS_FWD_MERGED   ptta_launch_loss_forward with emb and ref: the merged reduction + the finalisation
+ *        PTTA_LOSS_FWD_NOCOS    ptta_launch_loss_forward without the cosine term (emb, ref ignored)
+ *        PTTA_LOSS_FWD_SPLIT    loss_depth_part + loss_cos_part + loss_finalize (the fused step's branches); _SPLIT_NARROW: bf16 embeddings
+ *   bwd  PTTA_LOSS_BWD_NONE
+ *        PTTA_LOSS_BWD_UNFUSED  the separate depth and cosine gradient kernels reading the finalised workspace
+ *        PTTA_LOSS_BWD_FUSED    the forward launched with its finalisation deferred, then the gradient launch that finalises inside its
+ *                               kernels (merged depth + cosine kernel with emb and ref; fwd _MERGED or _NOCOS)
+ *        PTTA_LOSS_BWD_COUNTED  the thru step: loss_valid_count, loss_cos_part (fwd _SPLIT / _SPLIT_NARROW), loss_cos_coef, the depth
+ *                               gradient from the valid-weight partials, then the loss values (loss_depth_part + loss_finalize) and the
+ *                               cosine gradient kernel reading the coefficient from the workspace
+ * Outputs (each may be NULL): loss_info [4]; rowstats [r][3] = (|e|, |ref|, cos); gdepth [n][h][w]; gref [r][d]; coef [4 + n] =
+ * {coef_cos, coef_smx, coef_smy, n per-sample sparse-depth coefficients} read back from the workspace after the last launch, and in
+ * [3 + n] what loss_cos_coef alone left in the workspace (_COUNTED; untouched otherwise).
+ * -22: d not a multiple of 4 (8 for narrow embeddings), h < 2 or w < 2 (the smoothness counts divide by h - 1 and w - 1), r < 1 with a
+ * cosine term, a form combination outside the list above. */
+#define PTTA_LOSS_FWD_MERGED 0
+#define PTTA_LOSS_FWD_NOCOS 1
+#define PTTA_LOSS_FWD_SPLIT 2
+#define PTTA_LOSS_FWD_SPLIT_NARROW 3
+#define PTTA_LOSS_BWD_NONE 0
+#define PTTA_LOSS_BWD_UNFUSED 1
+#define PTTA_LOSS_BWD_FUSED 2
+#define PTTA_LOSS_BWD_COUNTED 3
+typedef struct ptta_loss_args {
+    int fwd, bwd, n, h, w, d;
+    long long r;
+    float max_input_depth, w_sd, w_sm, w_cos;
+    const float* depth; const float* image; const float* sparse; const float* validity; const float* emb; const float* ref;
+    float* loss_info; float* rowstats; float* gdepth; float* gref; float* coef;
+} ptta_loss_args;
+int ptta_op_loss(const ptta_loss_args* a, ptta_stream s);
 /* Diagnostic (tools/bench_chain.py): `reps` dependent launches of one stride-1 32->32 convolution (fp32 NHWC, default arithmetic) captured
  * into one hipGraph and replayed `replays` times: microseconds per launch INSIDE a replayed graph.  epi_flags: 2 = ReLU mask from `aux`,
  * 4 = skip addition of `aux`, 8 = the same chain launched directly (no graph), 16 = the layer loop (ONE launch per `reps` layers with a

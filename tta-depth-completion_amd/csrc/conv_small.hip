@@ -208,17 +208,20 @@ static int launch_conv_in_t(const ConvInArgs& a, hipStream_t s) {
     if (sizeof(T) == 4 && a.a_bits && a.a_bits_nb > 0 && !a.naive) { p.epi.bits_out = a.a_bits; p.epi.bits_nb = a.a_bits_nb; p.epi.bits_sum = 0; }
     if (sizeof(T) == 2 && a.mask && !a.mask_bits) return -22;
     p.B = a.B; p.H = a.H; p.W = a.W;
-    if (a.naive) {
+    const int form = ptta_conv_in_form(a);
+    if (form == CONV_IN_FORM_NAIVE) {
         p.w = a.wcanon;
         const long total = (long)p.B * p.H * p.W * 32;
         int blocks = (int)((total + 255) / 256); if (blocks > 8192) blocks = 8192;
+        if (a.max_blocks > 0 && blocks > a.max_blocks) blocks = a.max_blocks;
         hipLaunchKernelGGL((conv_in_naive_kernel<T>), dim3(blocks), dim3(256), 0, s, p, a.cin);
     } else {
         p.w = a.wfrag;
-        if (!a.up && !a.add1) {          // every use on the path: bias (+ ReLU mask in the backward) only
+        if (form != CONV_IN_FORM_DIRECT) {          // every use on the path: bias (+ ReLU mask in the backward) only
             const long tiles = (long)p.B * ((p.W + 31) / 32) * ((p.H + CI_TH - 1) / CI_TH);
-            const int blocks = (int)(tiles > 2048 ? 2048 : tiles);
-#define CL_(C) do { if (a.mask) hipLaunchKernelGGL((conv_in_lds_kernel<T, C, true>), dim3(blocks), dim3(256), 0, s, p); \
+            int blocks = (int)(tiles > 2048 ? 2048 : tiles);
+            if (a.max_blocks > 0 && blocks > a.max_blocks) blocks = a.max_blocks;
+#define CL_(C) do { if (form == CONV_IN_FORM_LDS_MASK) hipLaunchKernelGGL((conv_in_lds_kernel<T, C, true>), dim3(blocks), dim3(256), 0, s, p); \
                     else hipLaunchKernelGGL((conv_in_lds_kernel<T, C, false>), dim3(blocks), dim3(256), 0, s, p); } while (0)
             if (a.cin == 1) CL_(1); else if (a.cin == 2) CL_(2); else CL_(3);
 #undef CL_
@@ -227,12 +230,19 @@ static int launch_conv_in_t(const ConvInArgs& a, hipStream_t s) {
         }
         const long items = (long)p.B * ((p.W + 31) / 32) * p.H;
         long blocks = (items + 3) / 4; if (blocks > 2048) blocks = 2048;
+        if (a.max_blocks > 0 && blocks > a.max_blocks) blocks = a.max_blocks;
         if (a.cin == 1) hipLaunchKernelGGL((conv_in_mfma_kernel<T, 1>), dim3((int)blocks), dim3(256), 0, s, p);
         else if (a.cin == 2) hipLaunchKernelGGL((conv_in_mfma_kernel<T, 2>), dim3((int)blocks), dim3(256), 0, s, p);
         else hipLaunchKernelGGL((conv_in_mfma_kernel<T, 3>), dim3((int)blocks), dim3(256), 0, s, p);
     }
     PTTA_CHECK_LAUNCH();
     return 0;
+}
+
+int ptta_conv_in_form(const ConvInArgs& a) {
+    if (a.naive) return CONV_IN_FORM_NAIVE;
+    if (a.up || a.add1) return CONV_IN_FORM_DIRECT;
+    return a.mask ? CONV_IN_FORM_LDS_MASK : CONV_IN_FORM_LDS;
 }
 
 int ptta_launch_conv_in(const ConvInArgs& a, hipStream_t s) {
@@ -338,7 +348,8 @@ void ptta_pack_conv_out1(const float* src, int src_cin_total, int src_cin_index,
 int ptta_launch_conv_out1(const ConvOut1Args& a, hipStream_t s) {
     const int add_nb = a.add_nb > 0 ? a.add_nb : 1;
     const long tiles = (long)a.B * ((a.W + 31) / 32) * ((a.H + 7) / 8);
-    const int tb = (int)(tiles < 768 ? tiles : 768);                                            // three 43.5-KB blocks per CU
+    int tb = (int)(tiles < 768 ? tiles : 768);                                                  // three 43.5-KB blocks per CU
+    if (a.max_blocks > 0 && tb > a.max_blocks) tb = a.max_blocks;
 #define LDS_(T, R) hipLaunchKernelGGL((conv_out1_lds_kernel<T, R>), dim3(tb), dim3(256), 0, s, (const T*)a.in, a.in_nb, a.w, a.bias, a.add, add_nb, a.out, a.B, a.H, a.W)
     if (a.bf16) { if (a.relu_in) LDS_(bf16_t, true); else LDS_(bf16_t, false); }
     else { if (a.relu_in) LDS_(float, true); else LDS_(float, false); }

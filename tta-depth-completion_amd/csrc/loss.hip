@@ -15,8 +15,8 @@
 
 #define LOSS_PB 256          // depth-reduction blocks per sample (<= 256: one finalize thread each)
 #define LOSS_CB_MIN 1024     // cosine-reduction blocks (and partial slots) up to 131,072 rows; beyond: one slot per 128-row GEMM block
-#define WS_SCAL 0            // [0] coef_cos [1] coef_smx [2] coef_smy
-#define WS_SD 16             // per-sample w_sd / (N * sum_w)
+#define WS_SCAL PTTA_LOSS_WS_SCAL            // [0] coef_cos [1] coef_smx [2] coef_smy
+#define WS_SD PTTA_LOSS_WS_SD             // per-sample w_sd / (N * sum_w)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -196,7 +196,7 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
 // instead of as a 1-block launch between them: one ~20 us latency-bound kernel less on the step's critical path; the split API
 // (ptta_loss_forward) runs it as loss_finalize_kernel below.  fin (LDS): [0] coef_cos [1] cx [2] cy [3..3+N) per-sample sparse-depth
 // coefficient (first LOSS_FIN_MAXN samples); with `loss_info` given, the scalars and the coefficients also go to the workspace.
-#define LOSS_FIN_MAXN 16
+#define LOSS_FIN_MAXN PTTA_LOSS_FIN_MAXN
 __device__ void loss_finalize_block(const float* __restrict__ ws, int N, int H, int W, long R, int has_cos, const float* __restrict__ w3,
                                     float* __restrict__ fin, float* __restrict__ loss_info, float* __restrict__ ws_out) {
     __shared__ double red[4];

@@ -77,7 +77,11 @@ struct ConvInArgs {      // planar fp32 (cin = 1..3) -> 32-channel NHWC
     // fused first-kernel forms only (ptta_launch_conv32_first): sign bits of `mask` / bits of the a_out map
     const uint32_t* mask_bits = nullptr; uint32_t* a_bits = nullptr;
     int a_bits_nb = 0;              // unfused launch (fp32 output): also write the sign-bit plane `a_bits` of out_raw for frames b < a_bits_nb
+    int max_blocks = 0;             // > 0 caps the grid (tests: a small map then makes one block walk several tiles); 0 = the launcher's own rule
 };
+// the kernel ptta_launch_conv_in takes for these arguments
+enum { CONV_IN_FORM_LDS = 0, CONV_IN_FORM_LDS_MASK = 1, CONV_IN_FORM_DIRECT = 2, CONV_IN_FORM_NAIVE = 3 };
+int ptta_conv_in_form(const ConvInArgs& a);
 void ptta_pack_conv_in(const float* src, int cin_total, int cin_first, int cin, int transpose_flip,
                        float* wfrag, float* wcanon, hipStream_t s);
 int ptta_launch_conv_in(const ConvInArgs& a, hipStream_t s);
@@ -91,6 +95,7 @@ struct ConvOut1Args {    // 32-channel NHWC -> planar fp32, 1 channel
     const float* add = nullptr; int add_nb = 1;
     float* out = nullptr;
     int B = 1, H = 0, W = 0; int relu_in = 0; int bf16 = 0;
+    int max_blocks = 0;             // as ConvInArgs::max_blocks
 };
 void ptta_pack_conv_out1(const float* src, int src_cin_total, int src_cin_index, int from_conv_in, float* w, hipStream_t s);
 int ptta_launch_conv_out1(const ConvOut1Args& a, hipStream_t s);
@@ -216,6 +221,9 @@ int ptta_launch_hn_gemm(const HnGemmArgs& a, hipStream_t s);
 
 // ---- loss.hip ---------------------------------------------------------------------------------
 struct LossScalars;      // device-resident scalars, see loss.hip
+// workspace floats the finalisation leaves: [PTTA_LOSS_WS_SCAL + 0 .. 2] = coef_cos, coef_smx, coef_smy; [PTTA_LOSS_WS_SD + n] = per-sample w_sd / (N sum_w);
+// PTTA_LOSS_FIN_MAXN: the largest batch whose finalisation the fused gradient kernels run themselves (beyond it: the finalize kernel)
+enum { PTTA_LOSS_WS_SCAL = 0, PTTA_LOSS_WS_SD = 16, PTTA_LOSS_FIN_MAXN = 16 };
 int ptta_loss_ws_floats(int N, int H, int W, long R);
 long ptta_loss_ws_rows_off(int N);        // floats from the workspace start to the per-row statistics [R][3] = (|e|, |ref|, cos); [0] = the gated cosine coefficient
 int ptta_launch_loss_forward(const float* depth, const float* image, const float* sparse, const float* validity,

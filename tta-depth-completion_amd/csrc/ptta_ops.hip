@@ -1,6 +1,8 @@
 // Entry points that take no handle: outlier removal, evaluation metrics, the modulated deformable convolution, and the
 // stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_gconv, ptta_op_gconv_affine, ptta_op_gbn, ptta_op_conv32_chain,
-// and CostDCNet's own kernels: ptta_cd_sparse_*, ptta_op_cd_sparse_conv, ptta_op_cd_sbn, ptta_op_cd_densify, ptta_op_cd_dense).
+// CostDCNet's own kernels: ptta_cd_sparse_*, ptta_op_cd_sparse_conv, ptta_op_cd_sbn, ptta_op_cd_densify, ptta_op_cd_dense, and the MSG_CHN
+// step's first-layer / prediction convolutions, resamplings and loss: ptta_op_conv_in, ptta_op_conv_out1, ptta_op_prep, ptta_op_up2_1ch,
+// ptta_op_up2t_1ch, ptta_op_up2t_32, ptta_op_loss).
 #include "msgchn_ctx.h"
 #include "gnet.h"
 #include "costdc.h"
@@ -203,6 +205,224 @@ int ptta_op_conv32_tpair(const float* in, const float* weight1, const float* bia
     if (form < 0 || form > 2 || max_blocks < 0) return -22;
     return op_conv32_pair_body(in, weight1, bias1, weight2, bias2, up, add0, add1, add2, mask1_bits, mask2_bits, out_raw, out_sum, mid_raw, mid_sum,
                                mid_bits, b, in_nb, hin, win, first_mode, relu1, relu2, in_major, flip, dtype, w2, fused, fused_host, form, max_blocks, s_);
+}
+
+// ---- MSG_CHN's first-layer / prediction convolutions, resamplings and loss, stand-alone (tests/test_gpu_msgchn_elementwise.py) ----------
+// device allocations of one hook call, freed when it returns
+struct OpBufs {
+    std::vector<void*> v; bool ok = true;
+    void* get(size_t bytes) {
+        void* p = nullptr;
+        if (!ok || hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) { ok = false; return nullptr; }
+        v.push_back(p);
+        return p;
+    }
+    ~OpBufs() { for (void* p : v) (void)hipFree(p); }
+};
+static bool op_al(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1)) == 0; }
+// a 32-channel fp32 map in the launch's storage type: itself, or a narrow copy
+static const void* op_narrow_in(OpBufs& m, const float* src, long n, bool nar, hipStream_t s) {
+    if (!src || !nar) return src;
+    void* t = m.get((size_t)n * 2);
+    if (t) from_f32_launch(src, (bf16_t*)t, n, s);
+    return t;
+}
+// ... and an output: the caller's buffer, or a NaN-filled narrow one converted back by op_narrow_back
+static void* op_narrow_out(OpBufs& m, float* dst, long n, bool nar, hipStream_t s) {
+    if (!dst || !nar) return dst;
+    void* t = m.get((size_t)n * 2);
+    if (t) (void)hipMemsetAsync(t, 0xff, (size_t)n * 2, s);
+    return t;
+}
+static void op_narrow_back(const void* t, float* dst, long n, bool nar, hipStream_t s) {
+    if (dst && nar && t) to_f32_launch((const bf16_t*)t, dst, n, s);
+}
+
+int ptta_op_conv_in(const ptta_conv_in_args* a, int* form_host, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!a || !a->weight || (!a->out_raw && !a->out_sum) || a->cin < 1 || a->cin > 3 || a->b < 1 || a->h < 1 || a->w < 1 || a->zero_from_b < 0 ||
+        a->max_blocks < 0 || a->a_bits_nb < 0 || a->a_bits_nb > a->b) return -22;
+    if (a->transpose_flip ? a->cin != 1 : (a->cin_first < 0 || a->cin_total < 1 || a->cin_first + a->cin > a->cin_total)) return -22;
+    for (int c = 0; c < a->cin; ++c)
+        if (!a->pl[c].p || !op_al(a->pl[c].p, 4) || a->pl[c].nb < 1 || a->pl[c].nb > a->b) return -22;
+    const bool nar = a->dtype != PTTA_DTYPE_F32, hasmask = a->mask || a->mask_bits;
+    if (a->up && ((a->h & 1) || (a->w & 1) || a->up_nb < 1 || a->up_nb > a->b)) return -22;
+    if (hasmask && (a->mask_nb < 1 || a->mask_nb > a->b)) return -22;
+    if (a->add1 && (a->add1_nb < 1 || a->add1_nb > a->b || !a->out_sum)) return -22;
+    if (nar && a->mask && !a->mask_bits) return -22;            // the launcher's own refusal, ahead of the allocations
+    ConvInArgs k;
+    k.cin = a->cin; k.naive = a->naive ? 1 : 0; k.up = a->up; k.add1 = a->add1;
+    k.mask = a->mask ? (const void*)a->mask : (const void*)a->mask_bits;          // (non-null selects the masked kernels; a narrow launch reads the words only)
+    const int form = ptta_conv_in_form(k);
+    const bool lds = form == CONV_IN_FORM_LDS || form == CONV_IN_FORM_LDS_MASK;
+    if (!lds && hasmask && (nar || !a->mask)) return -22;      // the direct and naive kernels read the mask as a map of the storage type
+    if (a->a_bits && a->a_bits_nb > 0 && (nar || !lds)) return -22;
+    if (!op_al(a->up, 16) || !op_al(a->mask, 16) || !op_al(a->add1, 16) || !op_al(a->out_raw, 16) || !op_al(a->out_sum, 16) ||
+        !op_al(a->mask_bits, 4) || !op_al(a->a_bits, 4) || !op_al(a->weight, 4) || !op_al(a->bias, 4)) return -22;
+    const long plane = (long)a->h * a->w, nmap = (long)a->b * plane * 32;
+    OpBufs m;
+    float* wfrag = (float*)m.get(14 * 64 * 4);
+    float* wcanon = (float*)m.get(27 * 32 * 4);
+    if (wcanon) (void)hipMemsetAsync(wcanon, 0xff, 27 * 32 * 4, s);
+    k.up = op_narrow_in(m, a->up, (long)a->up_nb * (a->h / 2) * (a->w / 2) * 32, nar, s); k.up_nb = a->up_nb;
+    k.add1 = op_narrow_in(m, a->add1, (long)a->add1_nb * plane * 32, nar, s); k.add1_nb = a->add1_nb;
+    k.out_raw = op_narrow_out(m, a->out_raw, nmap, nar, s);
+    k.out_sum = op_narrow_out(m, a->out_sum, nmap, nar, s);
+    if (!m.ok) return -12;
+    ptta_pack_conv_in(a->weight, a->cin_total, a->cin_first, a->cin, a->transpose_flip, wfrag, wcanon, s);
+    for (int c = 0; c < a->cin; ++c) {
+        Plane& p = k.pl[c];
+        p.p = a->pl[c].p; p.nb = a->pl[c].nb; p.bstride = plane; p.norm = a->pl[c].norm ? 1 : 0;
+        p.div = a->pl[c].div; p.mean = a->pl[c].mean; p.stdv = a->pl[c].stdv;
+    }
+    k.zero_from_b = a->zero_from_b; k.wfrag = wfrag; k.wcanon = wcanon; k.bias = a->bias;
+    k.mask_nb = hasmask ? a->mask_nb : 1; k.mask_bits = a->mask_bits;
+    k.B = a->b; k.H = a->h; k.W = a->w; k.bf16 = nar ? 1 : 0;
+    k.a_bits = a->a_bits; k.a_bits_nb = a->a_bits ? a->a_bits_nb : 0; k.max_blocks = a->max_blocks;
+    int rc = ptta_launch_conv_in(k, s);
+    if (rc > 0) rc = -5;
+    if (!rc) { op_narrow_back(k.out_raw, a->out_raw, nmap, nar, s); op_narrow_back(k.out_sum, a->out_sum, nmap, nar, s); }
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    if (form_host) *form_host = form;
+    return rc;
+}
+
+int ptta_op_conv_out1(const ptta_conv_out1_args* a, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!a || !a->in || !a->weight || !a->out || a->b < 1 || a->h < 1 || a->w < 1 || a->in_nb < 1 || a->in_nb > a->b || a->max_blocks < 0) return -22;
+    if (a->add && (a->add_nb < 1 || a->add_nb > a->b)) return -22;
+    if (a->from_conv_in && (a->src_cin_total < 1 || a->src_cin_index < 0 || a->src_cin_index >= a->src_cin_total)) return -22;
+    if (!op_al(a->in, 16) || !op_al(a->weight, 4) || !op_al(a->bias, 4) || !op_al(a->add, 4) || !op_al(a->out, 4)) return -22;
+    const bool nar = a->dtype != PTTA_DTYPE_F32;
+    OpBufs m;
+    float* w = (float*)m.get(288 * 4);
+    ConvOut1Args k;
+    k.in = op_narrow_in(m, a->in, (long)a->in_nb * a->h * a->w * 32, nar, s); k.in_nb = a->in_nb;
+    if (!m.ok) return -12;
+    ptta_pack_conv_out1(a->weight, a->src_cin_total, a->src_cin_index, a->from_conv_in ? 1 : 0, w, s);
+    k.w = w; k.bias = a->bias; k.add = a->add; k.add_nb = a->add ? a->add_nb : 1; k.out = a->out;
+    k.B = a->b; k.H = a->h; k.W = a->w; k.relu_in = a->relu_in ? 1 : 0; k.bf16 = nar ? 1 : 0; k.max_blocks = a->max_blocks;
+    int rc = ptta_launch_conv_out1(k, s);
+    if (rc > 0) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+
+int ptta_op_prep(const float* sparse, float max_input_depth, float* dclamp, float* d12, float* d14, int n, int h, int w, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!sparse || !dclamp || !d12 || !d14 || n < 1 || h < 4 || w < 4 || (h & 3) || (w & 3) || !op_al(sparse, 16) || !op_al(dclamp, 16) ||
+        !op_al(d12, 4) || !op_al(d14, 4)) return -22;
+    int rc = ptta_launch_prep(sparse, max_input_depth, dclamp, d12, d14, n, h, w, s);
+    if (rc > 0) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+
+// (one block row per map row, one block plane per image: both are grid dimensions)
+static bool op_up2_ok(const void* a, const void* b, int n, int hin, int win) {
+    return a && b && n >= 1 && n <= 65535 && hin >= 1 && 2 * (long)hin <= 65535 && win >= 1 && win <= (1 << 20);
+}
+int ptta_op_up2_1ch(const float* in, float* out, int b, int hin, int win, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!op_up2_ok(in, out, b, hin, win) || !op_al(in, 4) || !op_al(out, 4)) return -22;
+    int rc = ptta_launch_up2_1ch(in, out, b, hin, win, s);
+    if (rc > 0) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+int ptta_op_up2t_1ch(const float* gout, float* gin, int b, int hin, int win, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!op_up2_ok(gout, gin, b, hin, win) || !op_al(gout, 4) || !op_al(gin, 4)) return -22;
+    int rc = ptta_launch_up2T_1ch(gout, gin, b, hin, win, s);
+    if (rc > 0) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+int ptta_op_up2t_32(const float* gout, const float* add, float* gin, int b, int hin, int win, int dtype, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!op_up2_ok(gout, gin, b, hin, win) || !op_al(gout, 16) || !op_al(add, 16) || !op_al(gin, 16)) return -22;
+    const bool nar = dtype != PTTA_DTYPE_F32;
+    const long nin = (long)b * hin * win * 32;
+    OpBufs m;
+    const void* g = op_narrow_in(m, gout, 4 * nin, nar, s);
+    const void* ad = op_narrow_in(m, add, nin, nar, s);
+    void* o = op_narrow_out(m, gin, nin, nar, s);
+    if (!m.ok) return -12;
+    int rc = ptta_launch_up2T_32(g, ad, o, b, hin, win, nar ? 1 : 0, s);
+    if (rc > 0) rc = -5;
+    if (!rc) op_narrow_back(o, gin, nin, nar, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+
+int ptta_op_loss(const ptta_loss_args* a, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!a || !a->depth || !a->image || !a->sparse || a->n < 1 || a->n > 65535 || a->h < 2 || a->w < 2 || a->fwd < PTTA_LOSS_FWD_MERGED ||
+        a->fwd > PTTA_LOSS_FWD_SPLIT_NARROW || a->bwd < PTTA_LOSS_BWD_NONE || a->bwd > PTTA_LOSS_BWD_COUNTED) return -22;
+    const bool cos = a->fwd != PTTA_LOSS_FWD_NOCOS, split = a->fwd >= PTTA_LOSS_FWD_SPLIT, nar = a->fwd == PTTA_LOSS_FWD_SPLIT_NARROW;
+    if (cos && (!a->emb || !a->ref || a->r < 1 || a->d < 4 || a->d % (nar ? 8 : 4) != 0 || !op_al(a->emb, 16) || !op_al(a->ref, 16) || !op_al(a->gref, 16))) return -22;
+    if (!cos && (a->gref || a->rowstats)) return -22;
+    if ((a->bwd == PTTA_LOSS_BWD_FUSED && split) || (a->bwd == PTTA_LOSS_BWD_COUNTED && !split)) return -22;
+    if (a->bwd != PTTA_LOSS_BWD_NONE ? !a->gdepth : (a->gdepth || a->gref)) return -22;
+    const int N = a->n, H = a->h, W = a->w, D = a->d;
+    const long R = cos ? (long)a->r : 0;
+    if ((double)N * H * W > 2.0e9 || (double)R * D > 2.0e9 || ptta_loss_ws_rows_off(N) + 3.0 * R > 2.0e9) return -22;
+    const long plane = (long)H * W, nws = ptta_loss_ws_floats(N, H, W, R);
+    OpBufs m;
+    float* ws = (float*)m.get((size_t)nws * 4);
+    float* w3 = (float*)m.get(16);
+    float* info = (float*)m.get(16);
+    float* gscratch = (a->bwd == PTTA_LOSS_BWD_COUNTED && a->gref) ? (float*)m.get((size_t)N * plane * 4) : nullptr;
+    const void *en = a->emb, *rn = a->ref;
+    if (nar) { en = op_narrow_in(m, a->emb, R * D, true, s); rn = op_narrow_in(m, a->ref, R * D, true, s); }
+    if (!m.ok) return -12;
+    (void)hipMemsetAsync(ws, 0xff, (size_t)nws * 4, s);
+    (void)hipMemsetAsync(info, 0xff, 16, s);
+    const float w3h[3] = {a->w_sd, a->w_sm, a->w_cos};
+    const float *e = cos ? a->emb : nullptr, *r = cos ? a->ref : nullptr;
+    const float maxd = a->max_input_depth;
+    int rc = ptta_launch_set_floats(w3, w3h, 3, s);
+#define OPL_(call) do { if (!rc) rc = (call); } while (0)
+    if (a->bwd != PTTA_LOSS_BWD_COUNTED) {
+        const int fused = a->bwd == PTTA_LOSS_BWD_FUSED;
+        if (!split) OPL_(ptta_launch_loss_forward(a->depth, a->image, a->sparse, a->validity, maxd, e, r, R, D, w3, N, H, W, ws, info, s, fused));
+        else {
+            OPL_(ptta_launch_loss_depth_part(a->depth, a->image, a->sparse, a->validity, maxd, N, H, W, ws, s));
+            OPL_(ptta_launch_loss_cos_part(en, rn, R, D, N, ws, s, nar ? 1 : 0));
+            OPL_(ptta_launch_loss_finalize(ws, N, H, W, R, 1, w3, info, s));
+        }
+        if (a->bwd == PTTA_LOSS_BWD_UNFUSED)
+            OPL_(ptta_launch_loss_backward(a->depth, a->image, a->sparse, a->validity, maxd, e, r, R, D, N, H, W, ws, a->gdepth, a->gref, s));
+        if (fused)
+            OPL_(ptta_launch_loss_backward(a->depth, a->image, a->sparse, a->validity, maxd, e, r, R, D, N, H, W, ws, a->gdepth, a->gref, s, w3, info));
+    } else {
+        // the thru step (msgchn_step.hip step_tail): the valid-weight partials first, the cosine rows and their coefficient, the depth gradient
+        // from the partials alone; the loss VALUES behind it (msgchn_backward.hip) -- in front of it beyond PTTA_LOSS_FIN_MAXN, where the
+        // gradient launch reads the finalised workspace
+        OPL_(ptta_launch_loss_valid_count(a->sparse, a->validity, N, H, W, ws, s));
+        OPL_(ptta_launch_loss_cos_part(en, rn, R, D, N, ws, s, nar ? 1 : 0));
+        OPL_(ptta_launch_loss_cos_coef(ws, N, R, w3, s));
+        if (!rc && a->coef && hipMemcpyAsync(a->coef + 3 + N, ws + PTTA_LOSS_WS_SCAL, 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = -5;
+        for (int pass = 0; pass < 2; ++pass) {
+            if ((N > PTTA_LOSS_FIN_MAXN) == (pass == 0)) {
+                OPL_(ptta_launch_loss_depth_part(a->depth, a->image, a->sparse, a->validity, maxd, N, H, W, ws, s));
+                OPL_(ptta_launch_loss_finalize(ws, N, H, W, R, 1, w3, info, s));
+            }
+            if (pass == 0)
+                OPL_(ptta_launch_loss_backward(a->depth, a->image, a->sparse, a->validity, maxd, nullptr, nullptr, R, D, N, H, W, ws, a->gdepth, nullptr, s,
+                                               w3, nullptr, 1, 1));
+        }
+        // the cosine gradient kernel reading the coefficient and the row statistics from the workspace (its depth half goes to scratch)
+        if (a->gref) OPL_(ptta_launch_loss_backward(a->depth, a->image, a->sparse, a->validity, maxd, a->emb, a->ref, R, D, N, H, W, ws, gscratch, a->gref, s));
+    }
+#undef OPL_
+    if (rc > 0) rc = -5;
+    auto d2d = [&](float* dst, const float* src, long n) { if (!rc && dst && n > 0 && hipMemcpyAsync(dst, src, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = -5; };
+    d2d(a->loss_info, info, 4);
+    if (cos) d2d(a->rowstats, ws + ptta_loss_ws_rows_off(N), 3 * R);
+    if (a->coef) { d2d(a->coef, ws + PTTA_LOSS_WS_SCAL, 3); d2d(a->coef + 3, ws + PTTA_LOSS_WS_SD, N); }
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
 }
 
 // Stand-alone weight + bias gradient of a stride-1 3x3 convolution on dense fp32 NHWC maps (tests, tools/bench_gwgrad_wide.py): the

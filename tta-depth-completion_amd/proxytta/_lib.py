@@ -60,6 +60,32 @@ class CdSbnArgs(ctypes.Structure):             # include/ptta.h ptta_cd_sbn_args
                 [(n, c_void_p) for n in ('f', 'res', 'y', 'g', 'gamma', 'beta', 'rm', 'rv', 'nbt', 'out', 'st', 'dgamma', 'dbeta', 'gx', 'gres')])
 
 
+class PlaneArg(ctypes.Structure):              # include/ptta.h ptta_plane
+    _fields_ = [('p', c_void_p), ('nb', c_int), ('norm', c_int), ('div', c_float), ('mean', c_float), ('stdv', c_float)]
+
+
+class ConvInArgs(ctypes.Structure):            # include/ptta.h ptta_conv_in_args
+    _fields_ = ([(n, c_int) for n in ('cin', 'cin_total', 'cin_first', 'transpose_flip', 'up_nb', 'mask_nb', 'add1_nb', 'a_bits_nb', 'zero_from_b', 'b',
+                                      'h', 'w', 'dtype', 'naive', 'max_blocks')] + [('pl', PlaneArg * 3)] +
+                [(n, c_void_p) for n in ('weight', 'bias', 'up', 'mask', 'mask_bits', 'add1', 'out_raw', 'out_sum', 'a_bits')])
+
+
+class ConvOut1Args(ctypes.Structure):          # include/ptta.h ptta_conv_out1_args
+    _fields_ = ([(n, c_int) for n in ('in_nb', 'src_cin_total', 'src_cin_index', 'from_conv_in', 'add_nb', 'relu_in', 'dtype', 'b', 'h', 'w', 'max_blocks')] +
+                [(n, c_void_p) for n in ('in', 'weight', 'bias', 'add', 'out')])
+
+
+class LossArgs(ctypes.Structure):              # include/ptta.h ptta_loss_args
+    _fields_ = ([(n, c_int) for n in ('fwd', 'bwd', 'n', 'h', 'w', 'd')] + [('r', ctypes.c_longlong)] +
+                [(n, c_float) for n in ('max_input_depth', 'w_sd', 'w_sm', 'w_cos')] +
+                [(n, c_void_p) for n in ('depth', 'image', 'sparse', 'validity', 'emb', 'ref', 'loss_info', 'rowstats', 'gdepth', 'gref', 'coef')])
+
+
+# ptta_op_loss `fwd` / `bwd`, ptta_op_conv_in's *form_host
+LOSS_FWD = {'merged': 0, 'nocos': 1, 'split': 2, 'split_narrow': 3}
+LOSS_BWD = {'none': 0, 'unfused': 1, 'fused': 2, 'counted': 3}
+CONV_IN_FORMS = ('lds', 'lds_mask', 'direct', 'naive')
+
 # ptta_op_cd_dense `op`
 CD_OPS = {'pad_dual': 0, 'crop_avg': 1, 'scatter_dual_grad': 2, 'stage': 3, 'clamp': 4, 'fusion_fwd': 5, 'fusion_bwd': 6, 'pool_fwd': 7,
           'pool_bwd': 8, 'up_fwd': 9, 'up_bwd': 10, 'regress_fwd': 11, 'regress_bwd': 12, 'rows_fwd': 13, 'rows_bwd': 14}
@@ -146,6 +172,13 @@ SIGNATURES = [
     ('ptta_op_cd_sbn', c_int, [_P, POINTER(CdSbnArgs), _P]),
     ('ptta_op_cd_densify', c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     ('ptta_op_cd_dense', c_int, [c_int, _P, _P, _P, _P, POINTER(c_int), POINTER(c_float), _P]),
+    ('ptta_op_conv_in', c_int, [POINTER(ConvInArgs), POINTER(c_int), _P]),
+    ('ptta_op_conv_out1', c_int, [POINTER(ConvOut1Args), _P]),
+    ('ptta_op_prep', c_int, [_P, c_float, _P, _P, _P, c_int, c_int, c_int, _P]),
+    ('ptta_op_up2_1ch', c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    ('ptta_op_up2t_1ch', c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    ('ptta_op_up2t_32', c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    ('ptta_op_loss', c_int, [POINTER(LossArgs), _P]),
     ('ptta_version', c_int, []),
 ]
 
@@ -190,4 +223,5 @@ def ptr(t):
     return c_void_p(t.data_ptr())
 
 
-__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'SIGNATURES', 'LIB_PATH', 'byref']
+__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs',
+           'LOSS_FWD', 'LOSS_BWD', 'CONV_IN_FORMS', 'SIGNATURES', 'LIB_PATH', 'byref']

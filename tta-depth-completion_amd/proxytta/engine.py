@@ -500,6 +500,99 @@ def op_conv32(x_nhwc, weight, bias, mode, relu_in=False, in_major=False, flip=Fa
     return out
 
 
+def _pv(t):
+    """Device pointer value of a tensor for a ctypes struct field (None -> NULL); the tensor must be contiguous."""
+    if t is None:
+        return None
+    assert t.is_contiguous() and t.is_cuda
+    return t.data_ptr()
+
+
+def op_conv_in(planes, weight, b, h, w, bias=None, cin_total=None, cin_first=0, transpose_flip=False, up=None, mask=None, mask_bits=None,
+               add1=None, out_raw=None, out_sum=None, a_bits=None, a_bits_nb=0, zero_from_b=1 << 30, dtype='fp32', naive=False, max_blocks=0):
+    """Test hook (include/ptta.h ptta_op_conv_in): the 1..3 -> 32 first-layer convolution.  planes: a list of (tensor [nb, h, w], norm) with
+    norm None or (div, mean, std); up / mask / add1 fp32 NHWC tensors whose first dimension is their frame count; mask_bits int32 [nb, h, w];
+    out_raw / out_sum / a_bits are written in place.  Returns the name of the kernel form that ran (_lib.CONV_IN_FORMS)."""
+    lib = _lib.load()
+    a = _lib.ConvInArgs()
+    a.cin, a.cin_total, a.cin_first, a.transpose_flip = len(planes), (cin_total if cin_total is not None else len(planes)), cin_first, int(transpose_flip)
+    a.up_nb = up.shape[0] if up is not None else 1
+    a.mask_nb = (mask if mask is not None else mask_bits).shape[0] if (mask is not None or mask_bits is not None) else 1
+    a.add1_nb = add1.shape[0] if add1 is not None else 1
+    a.a_bits_nb, a.zero_from_b, a.b, a.h, a.w = a_bits_nb, zero_from_b, b, h, w
+    a.dtype, a.naive, a.max_blocks = (0 if dtype == 'fp32' else 1), int(naive), max_blocks
+    for k, (t, norm) in enumerate(planes):
+        a.pl[k].p, a.pl[k].nb, a.pl[k].norm = _pv(t), t.shape[0], int(norm is not None)
+        a.pl[k].div, a.pl[k].mean, a.pl[k].stdv = norm if norm is not None else (1.0, 0.0, 1.0)
+    a.weight, a.bias, a.up, a.mask, a.mask_bits, a.add1 = _pv(weight), _pv(bias), _pv(up), _pv(mask), _pv(mask_bits), _pv(add1)
+    a.out_raw, a.out_sum, a.a_bits = _pv(out_raw), _pv(out_sum), _pv(a_bits)
+    form = c_int(-1)
+    rc = lib.ptta_op_conv_in(byref(a), byref(form), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_conv_in failed (%d)' % rc)
+    return _lib.CONV_IN_FORMS[form.value]
+
+
+def op_conv_out1(x_nhwc, weight, out, bias=None, add=None, relu_in=False, src_cin_total=0, src_cin_index=0, from_conv_in=False, dtype='fp32',
+                 max_blocks=0):
+    """Test hook (include/ptta.h ptta_op_conv_out1): the 32 -> 1 prediction convolution; out [b, h, w] is written in place, x_nhwc holds
+    in_nb <= b frames, add [add_nb, h, w]."""
+    lib = _lib.load()
+    a = _lib.ConvOut1Args()
+    a.in_nb, a.src_cin_total, a.src_cin_index, a.from_conv_in = x_nhwc.shape[0], src_cin_total, src_cin_index, int(from_conv_in)
+    a.add_nb, a.relu_in, a.dtype = (add.shape[0] if add is not None else 1), int(relu_in), (0 if dtype == 'fp32' else 1)
+    a.b, a.h, a.w, a.max_blocks = out.shape[0], out.shape[1], out.shape[2], max_blocks
+    setattr(a, 'in', _pv(x_nhwc))
+    a.weight, a.bias, a.add, a.out = _pv(weight), _pv(bias), _pv(add), _pv(out)
+    rc = lib.ptta_op_conv_out1(byref(a), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_conv_out1 failed (%d)' % rc)
+    return out
+
+
+def op_prep(sparse, max_input_depth, dclamp, d12, d14):
+    """Test hook (include/ptta.h ptta_op_prep): clamp + the 1/2 and 1/4 sparse-aware pooled maps of sparse [n, h, w], written in place."""
+    n, h, w = sparse.shape
+    rc = _lib.load().ptta_op_prep(ptr(sparse), float(max_input_depth), ptr(dclamp), ptr(d12), ptr(d14), n, h, w, _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_prep failed (%d)' % rc)
+
+
+def op_up2(x, out, transposed=False, add=None, dtype='fp32'):
+    """Test hooks (include/ptta.h ptta_op_up2_1ch / ptta_op_up2t_1ch / ptta_op_up2t_32): bilinear x2 of a planar map [b, hin, win] ->
+    out [b, 2 hin, 2 win], or its transpose x [b, 2 hin, 2 win(, 32)] -> out [b, hin, win(, 32)] (+ add, narrow storage: 32 channels only)."""
+    lib = _lib.load()
+    b, hin, win = (out if transposed else x).shape[:3]
+    if x.dim() == 4:
+        rc = lib.ptta_op_up2t_32(ptr(x), ptr(add), ptr(out), b, hin, win, 0 if dtype == 'fp32' else 1, _stream())
+    elif transposed:
+        rc = lib.ptta_op_up2t_1ch(ptr(x), ptr(out), b, hin, win, _stream())
+    else:
+        rc = lib.ptta_op_up2_1ch(ptr(x), ptr(out), b, hin, win, _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_up2 failed (%d)' % rc)
+    return out
+
+
+def op_loss(fwd, bwd, depth, image, sparse, w3, max_input_depth, validity=None, emb=None, ref=None, loss_info=None, rowstats=None, gdepth=None,
+            gref=None, coef=None, shape=None, r=None, d=None):
+    """Test hook (include/ptta.h ptta_op_loss): fwd / bwd keys of _lib.LOSS_FWD / _lib.LOSS_BWD; outputs are written in place.  shape / r / d
+    override what the tensors say (refusal tests)."""
+    lib = _lib.load()
+    a = _lib.LossArgs()
+    a.fwd, a.bwd = _lib.LOSS_FWD[fwd], _lib.LOSS_BWD[bwd]
+    a.n, a.h, a.w = shape if shape is not None else depth.shape
+    a.r = r if r is not None else (emb.shape[0] if emb is not None else 0)
+    a.d = d if d is not None else (emb.shape[1] if emb is not None else 0)
+    a.max_input_depth, (a.w_sd, a.w_sm, a.w_cos) = float(max_input_depth), w3
+    for name, t in (('depth', depth), ('image', image), ('sparse', sparse), ('validity', validity), ('emb', emb), ('ref', ref), ('loss_info', loss_info),
+                    ('rowstats', rowstats), ('gdepth', gdepth), ('gref', gref), ('coef', coef)):
+        setattr(a, name, _pv(t))
+    rc = lib.ptta_op_loss(byref(a), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_loss failed (%d)' % rc)
+
+
 GWGRAD_IMPLS = {'default': 0, 'fp32_mfma': 1, 'naive': 2}
 
 
