@@ -155,6 +155,24 @@ enum { PTTA_NLSPN_LEGACY_OFFSET = 0x100,
         *     affine).  ptta_head_* and the three exchange setters return -38.
         * Refused with -38 and a reason in ptta_last_error(NULL): another backbone, PTTA_META_2LAYERS, PTTA_SYNCBN_ADAPT, PTTA_DTYPE_MIXED. */
        PTTA_COSTDC_PLAIN = 0x800 };
+/* MSG_CHN, OR-ed into PTTA_META_1LAYER: the source model, network._forward (network_exp_msg_chn_adapt.py:402-403, :418-461) -- what loss_type
+ * 'pretrain' (the reference's default) runs, on a prepared model too: the loaded checkpoint without conv1_rgb_meta, without the zero-image
+ * pass and without the heads.  The three places that read the meta layer's output (depth_decoder1.dec1.3, depth_decoder2.dec2.3,
+ * depth_encoder3.enc2.3) read the RGB encoder's quarter-resolution map instead, and no meta convolution is launched.  fp32, one rank.
+ *   ptta_forward_eval only: the depth is `_forward`'s output_d11, the one scale the eval wrapper returns (src/msg_chn_model_adapt.py:179-181).
+ *     Sizes not divisible by 16 run the dual-corner padding and the mean of the two crops as on the ProxyTTA handle; ptta_set_image_norm and
+ *     the options that select launch forms of the forward ("graph", "pair_fuse", "tpair_fuse", "fuse_first") work.
+ *   ptta_adapted_count() and ptta_embedding_rows() are 0.  ptta_forward_train, ptta_step, ptta_step_pipelined, ptta_forward_eval_last,
+ *     ptta_pipeline_stream, ptta_backward, ptta_adam_step, ptta_loss_forward, ptta_loss_backward, every ptta_head_* and the three exchange
+ *     setters return -38 with a reason and leave the handle usable.  ptta_profile brackets the launches of the eval forward.
+ *   Activations are allocated for n frames, not 2 n (ptta_debug_tensor reports the halved sizes; "m" is an unknown name); the narrow copies,
+ *     the proxy-RGB constants, the heads' weights and workspace, the backward's 32 -> 32 weight packs, masks and gradient maps, the weight-gradient
+ *     partials and the Adam state are not allocated at all.
+ *   ptta_load_weights accepts a state dict without conv1_rgb_meta.*, proj* and pred* keys and ignores them when present, in their 1layer
+ *     and their 2layers form alike (a stage-3 checkpoint holds them).
+ * Refused at ptta_create with -38 and a reason in ptta_last_error(NULL): another backbone, PTTA_META_2LAYERS or PTTA_META_NONE as the base
+ * mode, PTTA_DTYPE_MIXED (the scored forward of the mixed mode is the fp32 one already), any other flag beside it. */
+enum { PTTA_MSGCHN_PLAIN = 0x1000 };
 
 /* Hyper-parameters of the step.  Reference: src/tta.py:10-160 flags learning_rates,
  * optimizer_betas, optimizer_epsilon, w_weight_decay, w_loss_sparse_depth, w_loss_smoothness,

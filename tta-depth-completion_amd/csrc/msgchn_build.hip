@@ -22,7 +22,7 @@ static const char* kRgb32[] = {"rgb_encoder.init.2", "rgb_encoder.enc1.1", "rgb_
 
 void build_registry(ptta_ctx* c) {
     auto add32 = [&](const std::string& n, int transposed, bool need_bwd) {
-        L32 l; l.f = alloc_convw(c); if (need_bwd) l.b = alloc_convw(c);
+        L32 l; l.f = alloc_convw(c); if (need_bwd && !c->plain) l.b = alloc_convw(c);        // (the source model has no backward)
         l.bias = c->falloc(32); l.transposed = transposed;
         c->l32[n] = l;
     };
@@ -46,6 +46,7 @@ void build_registry(ptta_ctx* c) {
         li.wfrag = c->falloc(14 * 64); li.wcanon = c->falloc(9 * 3 * 32); li.bias = c->falloc(32); li.bw = c->falloc(288);
         c->lin_in["rgb_encoder.init.0"] = li;
     }
+    if (c->plain) return;       // the source model (PTTA_MSGCHN_PLAIN): no meta layer, no heads
     {   // the adapted layer: forward fragments are re-packed from the bound parameter every forward
         L32 l; l.f = alloc_convw(c); l.bias = nullptr; c->l32["conv1_rgb_meta"] = l;
     }
@@ -74,11 +75,12 @@ void build_registry(ptta_ctx* c) {
 }
 
 void build_workspace(ptta_ctx* c) {
-    const int Nn = c->Nn, B2 = 2 * Nn;
+    // [real | proxy] maps hold 2 Nn frames; the source model (PTTA_MSGCHN_PLAIN) has one pass: every map holds Nn
+    const int Nn = c->Nn, B2 = c->plain ? Nn : 2 * Nn;
     const int H1 = c->Hp, W1 = c->Wp;
     c->H2 = H1 / 2; c->W2 = W1 / 2; c->H4 = H1 / 4; c->W4 = W1 / 4; c->H8 = H1 / 8; c->W8 = W1 / 8; c->H16 = H1 / 16; c->W16 = W1 / 16;
     const int H2 = c->H2, W2 = c->W2, H4 = c->H4, W4 = c->W4, H8 = c->H8, W8 = c->W8, H16 = c->H16, W16 = c->W16;
-    c->Rg = (long)Nn * H4 * W4;
+    c->Rg = c->plain ? 0 : (long)Nn * H4 * W4;
     if (c->dual) { c->img_pad = c->falloc((size_t)Nn * 3 * H1 * W1); c->sp_pad = c->falloc((size_t)Nn * H1 * W1); }
 #define A_(name, nb, h, w) c->name = c->act(#name, nb, h, w)
 #define M_(name, nb, h, w) c->name = c->map1(#name, nb, h, w)
@@ -86,7 +88,8 @@ void build_workspace(ptta_ctx* c) {
     M_(out1, B2, H4, W4); M_(p12, B2, H2, W2); M_(q, B2, H2, W2); M_(p11, B2, H1, W1);
     M_(depth_net, Nn, H1, W1); M_(depth_final, c->N, c->H, c->W); M_(validity_tmp, c->N, c->H, c->W);
     A_(c0a, B2, H1, W1); A_(c0, B2, H1, W1); A_(c1a, B2, H2, W2); A_(c1, B2, H2, W2);
-    A_(c2a, B2, H4, W4); A_(c2, B2, H4, W4); A_(m, B2, H4, W4);
+    A_(c2a, B2, H4, W4); A_(c2, B2, H4, W4);
+    if (c->plain) c->m = nullptr; else A_(m, B2, H4, W4);            // (ptta_ctx::meta_out: the source model reads c2 where the others read m)
     A_(c3a, B2, H8, W8); A_(c3, B2, H8, W8); A_(c4a, B2, H16, W16); A_(c4, B2, H16, W16);
     A_(e1_0a, Nn, H4, W4); A_(e1_0, Nn, H4, W4); A_(e1_1a, Nn, H8, W8); A_(e1_1, B2, H8, W8); A_(e1_2a, Nn, H16, W16);
     A_(y1, B2, H8, W8); A_(y2, B2, H16, W16); A_(t1, B2, H8, W8); A_(y3, B2, H8, W8); A_(s1_1, B2, H8, W8);
@@ -97,6 +100,13 @@ void build_workspace(ptta_ctx* c) {
     A_(e3_0a, B2, H1, W1); A_(e3_0, B2, H1, W1); A_(e3_1a, B2, H2, W2); A_(e3_1, B2, H2, W2); A_(e3_2a, B2, H4, W4);
     A_(feat, B2, H4, W4); A_(w2, B2, H4, W4);
     A_(t3, Nn, H2, W2); A_(s1_3, Nn, H2, W2); A_(u3, Nn, H1, W1); A_(s0_3, Nn, H1, W1); A_(v3, Nn, H1, W1);
+    if (c->plain) {
+        // the eval forward's maps are all the source model has: no ReLU masks, heads' workspace, loss workspace, gradient maps, weight-gradient
+        // partials, gradient arena, staged inputs or Adam table -- only the few words the shared entry points write
+        c->hyper = c->falloc(16); c->step_dev = (int*)c->dalloc(16);
+        c->stamp_f = c->falloc(16); c->stamp_base = (unsigned long long*)c->dalloc(8); c->dbg["stamps"] = Dbg{c->stamp_f, 16, 0};
+        return;
+    }
     {   // the ReLU masks of backbone_backward (real frames).  v1 is not listed: its only reader is the unfused conv^T_{1->32} kernel
         // (float mask); e*_0a only when the fused init block (conv32_first) is what writes them for every launch shape.
 #define MB_(name, h, w) c->mask_plane(c->name, Nn, h, w)
@@ -209,6 +219,8 @@ int load_weight(ptta_ctx* c, const std::string& name, const void* tensor, const 
     const long numel = shape_numel(shape, ndim);
     auto ends = [&](const char* suf) { const size_t n = strlen(suf); return name.size() >= n && name.compare(name.size() - n, n, suf) == 0; };
     if (name.rfind("proj_t.", 0) == 0) return 0;                     // EMA target head: unused in stage 3 (:551-554)
+    // the source model runs none of what _prepare_head adds: a stage-3 checkpoint's meta layer (1layer or 2layers keys) and heads are ignored
+    if (c->plain && (name.rfind("conv1_rgb_meta", 0) == 0 || name.rfind("proj", 0) == 0 || name.rfind("pred", 0) == 0)) return 0;
     if (name.rfind("conv1_rgb_meta", 0) == 0) {
         if (c->meta_mode == PTTA_META_2LAYERS) {           // BatchNorm2d buffers of Res_Conv: bound, updated in place
             const bool first = name.find("conv1_meta.0.1.") != std::string::npos, second = name.find("conv1_meta.2.") != std::string::npos;

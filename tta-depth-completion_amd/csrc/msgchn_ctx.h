@@ -24,6 +24,12 @@
 // calls forwarded to a GNet engine clear the wrapper-level message, so the engine's later message is not masked by a stale one
 #define NLFWD(call) do { if (c && c->nl) { c->err.clear(); return (call); } } while (0)
 
+// the source-model handle (include/ptta.h PTTA_MSGCHN_PLAIN) has the eval forward only: what it refuses, in the words of the other two
+// backbones' source handles
+#define PLAIN_NO_TRAIN(what) do { if (c && !c->nl && c->plain) return c->fail(std::string(what) + ": the source model (PTTA_MSGCHN_PLAIN) adapts nothing: it has the eval forward only", -38); } while (0)
+#define PLAIN_NO_HEADS(what) do { if (c && !c->nl && c->plain) return c->fail(std::string(what) + ": PTTA_MSGCHN_PLAIN: this handle runs the network without the meta layer and has no heads (no stage-2 head trainer)", -38); } while (0)
+#define PLAIN_ONE_RANK(what) do { if (c && !c->nl && c->plain) return c->fail(std::string(what) + ": PTTA_MSGCHN_PLAIN: more than one rank is not offered (no statistics or gradient exchange)", -38); } while (0)
+
 struct ImgNorm { int on; float div; float mean[3]; float stdv[3]; };
 
 // ---- the small utility kernels (msgchn_kernels.hip) behind host functions: each kernel is compiled once ----
@@ -91,6 +97,9 @@ struct ptta_ctx : PrefixBufs {
     std::map<std::string, Dbg> dbg;
     // adapted parameters (bound, caller-owned) in state_dict order; g = internal gradient buffer
     int meta_mode = 0;
+    // the source model (include/ptta.h PTTA_MSGCHN_PLAIN): no meta layer (its three readers take c2), one pass, no heads; eval forward only
+    int plain = 0;
+    void* meta_out() const { return plain ? c2 : m; }       // what depth_decoder1.dec1.3, depth_decoder2.dec2.3 and depth_encoder3.enc2.3 add
     struct Adapted { std::string name; long n = 0; float *p = nullptr, *m = nullptr, *v = nullptr, *g = nullptr; };
     std::vector<Adapted> adapted;
     // stage-2 head trainer: the twelve proj / pred parameters (bound like the adapted ones) + the six

@@ -152,8 +152,8 @@ int conv32_tpair(ptta_ctx* c, hipStream_t s, bool bwd, const std::string& first,
         Conv32Args f, g;
         if (tpair_takes(c, f, g, bwd, first, in, in_nb, B, Hin, Win, fe, second, mid_nb, se)) {
             // the map's only other reader is a backward that masks with the float map: fp32 storage without a bit plane (where there is one it
-            // covers the real frames, the only ones the backward masks)
-            if (!bwd && (nar || f.bits_out != nullptr)) { f.out_raw = nullptr; c->tpair_unwritten.insert(fe.raw); }
+            // covers the real frames, the only ones the backward masks); the source model has no backward: it never writes the map
+            if (!bwd && (nar || f.bits_out != nullptr || c->plain)) { f.out_raw = nullptr; c->tpair_unwritten.insert(fe.raw); }
             else if (!bwd) c->tpair_unwritten.erase(fe.raw);
             const int es_l = nar ? 2 : c->es;
             double b1, m1, b2, m2;
@@ -470,7 +470,7 @@ static int backbone(ptta_ctx* c, const float* image, bool train, hipStream_t s) 
     // train: the proxy half of c0..c4 (zero image through frozen weights) is a constant of the handle, computed once by
     // ensure_proxy_rgb(); only the real frames go through the encoder here
     if (!c->skip_prefix) RUN(rgb_encoder(c, image, Nn, 0, Nn, s));
-    RUN(meta_forward(c, train, B2, s));
+    if (!c->plain) RUN(meta_forward(c, train, B2, s));      // (the source model: the three readers of `m` take c2, ptta_ctx::meta_out)
     // ---- stage 1/4 (:487-489): depth-only encoder shared by both passes ----
     if (!c->skip_prefix) { RUN(enc1_head_fn(c, s)); RUN(stage1_independent(c, B2, s)); }
 
@@ -484,7 +484,7 @@ static int backbone(ptta_ctx* c, const float* image, bool train, hipStream_t s) 
         const void* e1_0 = nar ? c->tw(c->e1_0) : c->e1_0;
 #define CR(...) RUN(conv32(c, st, __VA_ARGS__))
         // decoder 1 (DepthDecoder.forward :296-311); its first three launches are in stage1_independent()
-        { E e; e.nar = nar; e.raw = A(c->y4, H4, W4); e.sum = A(c->s0_1, H4, W4); e.add1 = e1_0; e.add1_nb = Nn; e.add2 = A(c->m, H4, W4); e.add2_nb = Bl;
+        { E e; e.nar = nar; e.raw = A(c->y4, H4, W4); e.sum = A(c->s0_1, H4, W4); e.add1 = e1_0; e.add1_nb = Nn; e.add2 = A(c->meta_out(), H4, W4); e.add2_nb = Bl;
           CR("depth_decoder1.dec1.3", false, CONV_S1, A(c->u1, H4, W4), Bl, Bl, H4, W4, true, e); }
         CR("depth_decoder1.prdct.1", false, CONV_S1, A(c->s0_1, H4, W4), Bl, Bl, H4, W4, true, raw(A(c->v1, H4, W4)));
         {
@@ -504,7 +504,7 @@ static int backbone(ptta_ctx* c, const float* image, bool train, hipStream_t s) 
             a.B = Bl; a.H = H2; a.W = W2; a.bf16 = c->bf16; a.naive = c->naive;
             // (the pre-activation map is the backward's ReLU mask for the real frames only: batch indices below Nn of a launch that starts at b0 = 0)
             E e; e.nar = nar; e.raw = A(c->e2_0, H2, W2); e.up = A(c->y4, H4, W4); e.up_nb = Bl;
-            RUN(conv32_first(c, st, "depth_encoder2.init.2", a, (b0 == 0 && !nar) ? Nn : 0, Bl, H2, W2, e));
+            RUN(conv32_first(c, st, "depth_encoder2.init.2", a, (b0 == 0 && !nar && !c->plain) ? Nn : 0, Bl, H2, W2, e));
         }
         // (each stride-2 layer and the stride-1 layer behind it: one launch on small maps, conv32_pair)
         { E e; e.nar = nar; e.raw = A(c->e2_1, H4, W4); e.up = A(c->y3, H8, W8); e.up_nb = Bl;
@@ -512,7 +512,7 @@ static int backbone(ptta_ctx* c, const float* image, bool train, hipStream_t s) 
         { E e; e.nar = nar; e.sum = A(c->z2, H8, W8); e.up = A(c->y2, H16, W16); e.up_nb = Bl; e.add1 = A(c->c3, H8, W8); e.add1_nb = Bl;            // z2 = e2_2 + c3
           RUN(conv32_pair(c, st, false, "depth_encoder2.enc2.1", A(c->e2_1, H4, W4), Bl, Bl, H4, W4, raw(A(c->e2_2a, H8, W8)), "depth_encoder2.enc2.3", Bl, e)); }
         // (each transposed layer and the stride-1 layer behind it: one launch, conv32_tpair)
-        { E e; e.nar = nar; e.raw = A(c->z3, H4, W4); e.sum = A(c->s1_2, H4, W4); e.add1 = A(c->e2_1, H4, W4); e.add1_nb = Bl; e.add2 = A(c->m, H4, W4); e.add2_nb = Bl;
+        { E e; e.nar = nar; e.raw = A(c->z3, H4, W4); e.sum = A(c->s1_2, H4, W4); e.add1 = A(c->e2_1, H4, W4); e.add1_nb = Bl; e.add2 = A(c->meta_out(), H4, W4); e.add2_nb = Bl;
           RUN(conv32_tpair(c, st, false, "depth_decoder2.dec2.1", A(c->z2, H8, W8), Bl, Bl, H8, W8, raw(A(c->t2, H4, W4)), "depth_decoder2.dec2.3", Bl, e)); }
         { E e; e.nar = nar; e.raw = A(c->z4, H2, W2); e.sum = A(c->s0_2, H2, W2); e.add1 = A(c->e2_0, H2, W2); e.add1_nb = Bl; e.add2 = A(c->c1, H2, W2); e.add2_nb = Bl;
           RUN(conv32_tpair(c, st, false, "depth_decoder2.dec1.1", A(c->s1_2, H4, W4), Bl, Bl, H4, W4, raw(A(c->u2, H2, W2)), "depth_decoder2.dec1.3", Bl, e)); }
@@ -533,11 +533,11 @@ static int backbone(ptta_ctx* c, const float* image, bool train, hipStream_t s) 
             a.wfrag = li.wfrag; a.wcanon = li.wcanon; a.bias = li.bias; a.out_raw = A(c->e3_0a, H1, W1);
             a.B = Bl; a.H = H1; a.W = W1; a.bf16 = c->bf16; a.naive = c->naive;
             E e; e.nar = nar; e.raw = A(c->e3_0, H1, W1); e.up = A(c->z4, H2, W2); e.up_nb = Bl;
-            RUN(conv32_first(c, st, "depth_encoder3.init.2", a, (b0 == 0 && !nar) ? Nn : 0, Bl, H1, W1, e));
+            RUN(conv32_first(c, st, "depth_encoder3.init.2", a, (b0 == 0 && !nar && !c->plain) ? Nn : 0, Bl, H1, W1, e));
         }
         CR("depth_encoder3.enc1.1", false, CONV_S2, A(c->e3_0, H1, W1), Bl, Bl, H1, W1, true, raw(A(c->e3_1a, H2, W2)));
         { E e; e.nar = nar; e.raw = A(c->e3_1, H2, W2); e.up = A(c->z3, H4, W4); e.up_nb = Bl; CR("depth_encoder3.enc1.3", false, CONV_S1, A(c->e3_1a, H2, W2), Bl, Bl, H2, W2, true, e); }
-        { E e; e.nar = nar; e.raw = A(c->feat, H4, W4); e.up = A(c->z2, H8, W8); e.up_nb = Bl; e.add1 = A(c->m, H4, W4); e.add1_nb = Bl;   // w2 = feat + m
+        { E e; e.nar = nar; e.raw = A(c->feat, H4, W4); e.up = A(c->z2, H8, W8); e.up_nb = Bl; e.add1 = A(c->meta_out(), H4, W4); e.add1_nb = Bl;   // w2 = feat + m
           if (!nar) e.sum = A(c->w2, H4, W4); else e.add1 = nullptr;         // (the proxy pass stops at depth_encoder3: its w2 feeds nothing)
           RUN(conv32_pair(c, st, false, "depth_encoder3.enc2.1", A(c->e3_1, H2, W2), Bl, Bl, H2, W2, raw(A(c->e3_2a, H4, W4)), "depth_encoder3.enc2.3", Bl, e)); }
 #undef CR
@@ -799,7 +799,7 @@ int forward_common(ptta_ctx* c, const float* image, const float* sparse, bool tr
             ptta_pack_conv32(c->adapted[3].p, c->m2.w2f[g], 0, 0, s, 128, 32 * g);                 // W2 columns 32g..
             ptta_pack_conv32(c->adapted[3].p, c->m2.w2b[g], 1, 1, s, 128, 32 * g);                 // its input gradient
         }
-    } else {
+    } else if (!c->plain) {
         c->stamp(0, s);
         const L32& ml = c->l32["conv1_rgb_meta"];
         { ProfScope ps_(c, 8, s, 0, 0, 1); ptta_pack_conv32(c->meta_w, ml.f, 0, 0, s); }

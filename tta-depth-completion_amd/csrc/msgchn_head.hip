@@ -69,6 +69,7 @@ extern "C" {
 int ptta_head_set_form(ptta_handle c, int form) {
     if (!c) return -1;
     NLFWD(c->nl->head_set_form(form));
+    PLAIN_NO_HEADS("ptta_head_set_form");
     if (form != PTTA_HEAD_FORM_PLAIN && form != PTTA_HEAD_FORM_SYNCBN) return c->fail("ptta_head_set_form: PTTA_HEAD_FORM_PLAIN or PTTA_HEAD_FORM_SYNCBN", -22);
     if (c->head.stepped) return c->fail("ptta_head_set_form: the form is chosen before the first head step", -3);
     if (form == PTTA_HEAD_FORM_SYNCBN && c->mixed) return c->fail("the SyncBatchNorm form of the stage-2 head trainer needs an fp32 handle", -38);
@@ -79,6 +80,7 @@ int ptta_head_set_form(ptta_handle c, int form) {
 int ptta_head_bind(ptta_handle c, const char* name_, float* param, float* exp_avg, float* exp_avg_sq) {
     if (!c || !name_ || !param) return -1;
     NLFWD(c->nl->head_bind(name_, param, exp_avg, exp_avg_sq));
+    PLAIN_NO_HEADS("ptta_head_bind");
     RUN(head_init(c));
     const std::string name(name_);
     auto& h = c->head;
@@ -95,6 +97,7 @@ int ptta_head_set_hparams(ptta_handle c, float lr, float beta1, float beta2, flo
                           ptta_stream s_) {
     if (!c) return -1;
     NLFWD(c->nl->head_set_hparams(lr, beta1, beta2, eps, weight_decay, tau, adam_step, (hipStream_t)s_));
+    PLAIN_NO_HEADS("ptta_head_set_hparams");
     RUN(head_init(c));
     hipStream_t s = (hipStream_t)s_;
     const float hy[5] = {lr, beta1, beta2, eps, weight_decay};
@@ -108,6 +111,7 @@ int ptta_head_set_hparams(ptta_handle c, float lr, float beta1, float beta2, flo
 int ptta_head_reload(ptta_handle c, ptta_stream s) {
     if (!c) return -1;
     NLFWD(c->nl->head_reload((hipStream_t)s));
+    PLAIN_NO_HEADS("ptta_head_reload");
     RUN(head_init(c));
     c->drop_graphs();
     for (int k = 0; k < 12; ++k) RUN(head_reload(c, k, (hipStream_t)s));
@@ -117,6 +121,7 @@ int ptta_head_reload(ptta_handle c, ptta_stream s) {
 int ptta_head_forward(ptta_handle c, const float* image, const float* sparse, int reverse, float* emb_out, float* ref_out, ptta_stream s_) {
     if (!c || !image || !sparse) return -1;
     NLFWD(c->nl->head_forward(image, sparse, reverse, emb_out, ref_out, (hipStream_t)s_));
+    PLAIN_NO_HEADS("ptta_head_forward");
     RUN(head_init(c));
     auto& h = c->head;
     hipStream_t s = (hipStream_t)s_;
@@ -152,6 +157,7 @@ int ptta_head_forward(ptta_handle c, const float* image, const float* sparse, in
 int ptta_head_backward(ptta_handle c, float* loss_out, ptta_stream s_) {
     if (!c) return -1;
     NLFWD(c->nl->head_backward(loss_out, (hipStream_t)s_));
+    PLAIN_NO_HEADS("ptta_head_backward");
     auto& h = c->head;
     if (!h.ready || !h.fwd_ok) return c->fail("ptta_head_backward needs the activations of the last ptta_head_forward", -3);
     hipStream_t s = (hipStream_t)s_;
@@ -204,6 +210,7 @@ int ptta_head_backward(ptta_handle c, float* loss_out, ptta_stream s_) {
 int ptta_head_adam_step(ptta_handle c, ptta_stream s_) {
     if (!c) return -1;
     NLFWD(c->nl->head_adam_step((hipStream_t)s_));
+    PLAIN_NO_HEADS("ptta_head_adam_step");
     auto& h = c->head;
     if (!h.ready || !h.bwd_ok) return c->fail("ptta_head_adam_step needs the gradients of ptta_head_backward", -3);
     hipStream_t s = (hipStream_t)s_;
@@ -233,6 +240,7 @@ int ptta_head_step(ptta_handle c, const float* image, const float* sparse, int r
         if (!rc) rc = c->nl->head_backward(loss_out, (hipStream_t)s);
         return rc ? rc : c->nl->head_adam_step((hipStream_t)s);
     }
+    PLAIN_NO_HEADS("ptta_head_step");
     RUN(ptta_head_forward(c, image, sparse, reverse, nullptr, nullptr, s));
     RUN(ptta_head_backward(c, loss_out, s));
     return ptta_head_adam_step(c, s);
@@ -241,6 +249,7 @@ int ptta_head_step(ptta_handle c, const float* image, const float* sparse, int r
 int ptta_head_get_grad(ptta_handle c, const char* name, float* dst, int64_t capacity, int* has_grad_host, ptta_stream s) {
     if (!c || !name) return -1;
     NLFWD(c->nl->head_get_grad(name, dst, capacity, has_grad_host, (hipStream_t)s));
+    PLAIN_NO_HEADS("ptta_head_get_grad");
     auto& h = c->head;
     if (!h.ready) return c->fail("no head parameter bound", -3);
     for (int k = 0; k < 12; ++k) if (h.prm[k].name == name) {

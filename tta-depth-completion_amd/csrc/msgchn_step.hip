@@ -186,6 +186,7 @@ int ptta_step(ptta_handle c, const float* image, const float* loss_image, const 
     if (c) c->err_code = 0;
     if (!c || !image || !sparse) return -1;
     if (c->nl) return c->nl->step(image, loss_image, sparse, validity, depth_out, loss_info_out, (hipStream_t)s_);
+    PLAIN_NO_TRAIN("ptta_step");
     RUN(pipe_quiesce(c));
     hipStream_t s = (hipStream_t)s_;
     if (!loss_image) loss_image = image;
@@ -228,6 +229,7 @@ int ptta_step(ptta_handle c, const float* image, const float* loss_image, const 
 int ptta_pipeline_stream(ptta_handle c, ptta_stream* out) {
     if (!c || !out) return -1;
     if (c->nl) return c->fail("frame pipelining is built for MSG_CHN handles", -38);
+    PLAIN_NO_TRAIN("ptta_pipeline_stream");
     RUN(pipe_init(c));
     *out = (ptta_stream)c->pre_stream;
     return 0;
@@ -242,6 +244,7 @@ int ptta_step_pipelined(ptta_handle c, const float* image, const float* loss_ima
                         const float* next_image, const float* next_sparse, uint64_t next_token, float* depth_out, float* loss_info_out, ptta_stream s_) {
     if (c) c->err_code = 0;
     if (!c || !image || !sparse) return -1;
+    PLAIN_NO_TRAIN("ptta_step_pipelined");
     if (c->nl || c->prof_on || c->dual || c->stat_sync.on() || c->grad_comm || c->naive || c->bf16) {
         const int rc = ptta_step(c, image, loss_image, sparse, validity, depth_out, loss_info_out, s_);
         if (!c->nl) { c->fb_image = rc ? nullptr : image; c->fb_sparse = rc ? nullptr : sparse; }       // for ptta_forward_eval_last

@@ -46,6 +46,13 @@ int ptta_create(ptta_handle* out, int backbone_id, int meta_mode, int n, int hei
     if (!out) return -1;
     *out = nullptr;
     g_create_err.clear();
+    // MSG_CHN's source model (include/ptta.h PTTA_MSGCHN_PLAIN): `_forward` in fp32 on one rank, the eval forward only; refused before anything
+    // is allocated
+    if (meta_mode & PTTA_MSGCHN_PLAIN) {
+        if (backbone_id != PTTA_BACKBONE_MSG_CHN) return create_refused("PTTA_MSGCHN_PLAIN: the flag belongs to the MSG_CHN backbone (NLSPN has PTTA_META_NONE, CostDCNet PTTA_COSTDC_PLAIN)");
+        if ((meta_mode & 0xff) != PTTA_META_1LAYER) return create_refused("PTTA_MSGCHN_PLAIN with PTTA_META_2LAYERS or PTTA_META_NONE: the flag itself takes the meta layer out, its base mode is PTTA_META_1LAYER");
+        if ((dtype & 0xff) == PTTA_DTYPE_MIXED) return create_refused("PTTA_MSGCHN_PLAIN with PTTA_DTYPE_MIXED: the scored forward of the mixed mode is the fp32 one already");
+    }
     // no meta layer (include/ptta.h PTTA_META_NONE): NLSPN's `_forward` in fp32 on one rank -- the BatchNorm-adaptation baseline, or with
     // PTTA_ADAPT_META_ONLY the source model; refused before anything is allocated
     if ((meta_mode & 0xff) == PTTA_META_NONE) {
@@ -100,12 +107,15 @@ int ptta_create(ptta_handle* out, int backbone_id, int meta_mode, int n, int hei
                                 (plain ? 4 : 0) | ((plain && (meta_mode & PTTA_ADAPT_META_ONLY)) ? 8 : 0), &rc);
         return wrap_gnet(out, e, rc, gmix, n, height, width, hp);
     }
+    const int plain = (meta_mode & PTTA_MSGCHN_PLAIN) ? 1 : 0;          // (its backbone, base mode and dtype were checked above)
+    meta_mode &= ~PTTA_MSGCHN_PLAIN;
+    if (plain && meta_mode != PTTA_META_1LAYER) return create_refused("PTTA_MSGCHN_PLAIN takes no other flag beside it");
     if (backbone_id != PTTA_BACKBONE_MSG_CHN || (meta_mode != PTTA_META_1LAYER && meta_mode != PTTA_META_2LAYERS)) return -38;
     const int keep = (dtype >> 8) & 7;                 // PTTA_MIXED_KEEP_*: classes kept at fp32 / bf16x3 (precision budget)
     dtype &= 0xff;
     if (n < 1 || height < 16 || width < 16 || (dtype != PTTA_DTYPE_F32 && dtype != PTTA_DTYPE_MIXED) || !hp) return -22;
     ptta_ctx* c = new ptta_ctx();
-    c->meta_mode = meta_mode;
+    c->meta_mode = meta_mode; c->plain = plain;
     c->N = n; c->H = height; c->W = width; c->pt = pad16(height); c->pr = pad16(width);
     c->Hp = height + c->pt; c->Wp = width + c->pr; c->dual = (c->pt || c->pr) ? 1 : 0; c->Nn = c->dual ? 2 * n : n;
     c->mixed = dtype == PTTA_DTYPE_MIXED ? 1 : 0;
@@ -242,6 +252,7 @@ int ptta_forward_train(ptta_handle c, const float* image, const float* sparse, f
     NLFWD(c->nl->forward_train(image, sparse, depth_out, emb_out, ref_out, (hipStream_t)s_));
 
     if (!c || !image || !sparse) return -1;
+    PLAIN_NO_TRAIN("ptta_forward_train");
     hipStream_t s = (hipStream_t)s_;
     if (c->pipe_active && !c->skip_prefix) {              // never the buffer set a prefix may be writing (ptta_step_pipelined) ...
         pipe_use(c, c->pipe_last);
@@ -281,6 +292,7 @@ int ptta_forward_eval(ptta_handle c, const float* image, const float* sparse, fl
 int ptta_forward_eval_last(ptta_handle c, float* depth_out, ptta_stream s_) {
     if (!c || !depth_out) return -1;
     if (c->nl) return c->fail("ptta_forward_eval_last follows ptta_step_pipelined (MSG_CHN handles)", -38);
+    PLAIN_NO_TRAIN("ptta_forward_eval_last");
     if (!c->pipe_active) {
         // the last ptta_step_pipelined call ran as a plain ptta_step (no graph replay, profiling, SyncBatchNorm / gradient exchange, padded
         // sizes, bf16 storage ...): no prefix is held, so this is a full eval forward of that call's frame (its buffers are still the caller's)
@@ -308,6 +320,7 @@ int ptta_loss_forward(ptta_handle c, const float* loss_image, const float* depth
     NLFWD(c->nl->loss_forward(loss_image, depth, sparse, validity, emb, ref, rows, w_sd, w_sm, w_cos, loss_info_out, (hipStream_t)s_));
 
     if (!c || !loss_image || !depth || !sparse || !validity || !loss_info_out) return -1;
+    PLAIN_NO_TRAIN("ptta_loss_forward");
     if (rows > c->Rg) return c->fail("rows exceeds the handle's embedding rows", -22);
     hipStream_t s = (hipStream_t)s_;
     const float w3[3] = {w_sd, w_sm, w_cos};
@@ -322,6 +335,7 @@ int ptta_loss_backward(ptta_handle c, const float* loss_image, const float* dept
     NLFWD(c->nl->loss_backward(loss_image, depth, sparse, validity, emb, ref, rows, gdepth, gref, (hipStream_t)s_));
 
     if (!c || !loss_image || !depth || !sparse || !validity || !gdepth) return -1;
+    PLAIN_NO_TRAIN("ptta_loss_backward");
     RUN(ptta_launch_loss_backward(depth, loss_image, sparse, validity, c->hp.max_input_depth, emb, ref, rows, 512,
                                   c->N, c->H, c->W, c->loss_ws, gdepth, gref, (hipStream_t)s_));
     return 0;
@@ -331,6 +345,7 @@ int ptta_backward(ptta_handle c, const float* grad_depth, const float* grad_ref,
     NLFWD(grad_depth ? c->nl->backward_from(grad_depth, grad_ref, (hipStream_t)s_) : -1);   // gradients: ptta_get_grad
 
     if (!c || !grad_depth) return -1;
+    PLAIN_NO_TRAIN("ptta_backward");
     if (!c->fwd_valid) return c->fail("ptta_backward without a preceding ptta_forward_train", -3);
     hipStream_t s = (hipStream_t)s_;
     const float* g_net = grad_depth;
@@ -360,6 +375,7 @@ int ptta_adam_step(ptta_handle c, const float* gw, const float* gb, ptta_stream 
     if (c && c->nl) { c->err.clear(); return (gw || gb) ? c->fail("explicit gradients are an MSG_CHN 1layer convenience", -22) : c->nl->adam_step_checked((hipStream_t)s_); }
 
     if (!c) return -1;
+    PLAIN_NO_TRAIN("ptta_adam_step");
     for (auto& ad : c->adapted) if (!ad.p || !ad.m || !ad.v) return c->fail("Adam state of " + ad.name + " not bound", -3);
     if ((gw || gb) && c->meta_mode != PTTA_META_1LAYER) return c->fail("explicit gradients are a 1layer convenience; use the internal ones", -22);
     hipStream_t s = (hipStream_t)s_;
@@ -403,6 +419,7 @@ static int set_stat_sync(ptta_ctx* c, const PttaStatSync& sy, bool on, bool keep
     if (c->nl && !c->nl->one_rank_why.empty()) { c->err.clear(); return c->nl->fail(c->nl->one_rank_why, -38); }
     if (c->nl && c->nl->meta_only) { c->err.clear(); return c->nl->fail("the SyncBatchNorm form of the meta-only adaptation mode is not offered (PTTA_ADAPT_META_ONLY)", -38); }
     if (c->nl) { c->err.clear(); c->nl->drop_graphs(); c->nl->stat_sync = sy; return 0; }
+    PLAIN_ONE_RANK("statistics exchange");
     if (on && c->meta_mode == PTTA_META_2LAYERS && !c->m2.generic) return c->fail("SyncBatchNorm needs the default arithmetic for the 2layers meta layer", -38);
     c->stat_sync = sy;
     c->drop_graphs();
@@ -441,6 +458,7 @@ int ptta_set_grad_sync_rccl(ptta_handle c, void* comm) {
     if (c->nl && !c->nl->one_rank_why.empty()) { c->err.clear(); return c->nl->fail(c->nl->one_rank_why, -38); }
     if (c->nl && c->nl->meta_only) { c->err.clear(); return c->nl->fail("no gradient exchange in the meta-only adaptation mode: more than one rank is not offered (PTTA_ADAPT_META_ONLY)", -38); }
     if (c->nl) { c->nl->drop_graphs(); c->nl->grad_comm = comm; return 0; }
+    PLAIN_ONE_RANK("ptta_set_grad_sync_rccl");
     c->grad_comm = comm;
     c->drop_graphs();
     return 0;
@@ -508,7 +526,7 @@ int ptta_get_option(ptta_handle c, const char* key, int* value) {
     // read-only: 1 when ptta_step_pipelined would run as itself on this handle as it is configured now, 0 when it degrades to ptta_step
     // call by call (generic-engine backbones, the dual-corner padded path, a statistics exchange or gradient communicator bound, validation
     // arithmetic, the profiling leg)
-    if (k == "pipelined_active") { *value = !(c->nl || c->prof_on || c->dual || c->stat_sync.on() || c->grad_comm || c->naive || c->bf16); return 0; }
+    if (k == "pipelined_active") { *value = !(c->nl || c->plain || c->prof_on || c->dual || c->stat_sync.on() || c->grad_comm || c->naive || c->bf16); return 0; }
     // read-only: 1 when the step takes the two-stream `thru` schedule (loss gradient from the valid-weight partials), as far as it can be known
     // without the caller's stream (the second stream is created on first use)
     if (k == "thru_active") { *value = c->nl ? 0 : (c->thru && c->cos_grad_fused && heads_v2_on(c) && c->use_aux); return 0; }

@@ -21,6 +21,7 @@ PTTA_NLSPN_SYNCBN_ADAPT = 0x200
 PTTA_SYNCBN_ADAPT = 0x200
 PTTA_ADAPT_META_ONLY = 0x400
 PTTA_COSTDC_PLAIN = 0x800      # CostDCNet without the meta layer (with PTTA_ADAPT_META_ONLY: the source model)
+PTTA_MSGCHN_PLAIN = 0x1000     # MSG_CHN without the meta layer: the source model (eval forward only)
 PTTA_META_1LAYER = 0
 PTTA_META_2LAYERS = 1
 PTTA_META_NONE = 2             # NLSPN without the meta layer: the source model / the BatchNorm-adaptation baseline

@@ -68,10 +68,12 @@ class Engine:
         # meta 'none' (NLSPN): the network without the meta layer, one pass, no heads (include/ptta.h PTTA_META_NONE) -- with adapt_mode 'meta_bn'
         # the BatchNorm-adaptation baseline (86 adapted tensors), with 'meta' / 'meta_fix' the source model (nothing adapts, eval forward only)
         # meta 'plain' (CostDCNet): the same for that backbone (include/ptta.h PTTA_COSTDC_PLAIN): 30 adapted tensors / the source model
+        # meta 'plain' (MSG_CHN): the source model alone (include/ptta.h PTTA_MSGCHN_PLAIN): nothing adapts, forward_eval and load_state_dict work,
+        # every other call raises the library's reason
         if meta not in ('1layer', '2layers', 'none', 'plain'):
-            raise ValueError("meta must be '1layer', '2layers', 'none' (NLSPN) or 'plain' (CostDCNet)")
-        if meta == 'plain' and backbone != 'costdcnet':
-            raise ValueError("meta 'plain' belongs to the CostDCNet backbone (NLSPN has 'none')")
+            raise ValueError("meta must be '1layer', '2layers', 'none' (NLSPN) or 'plain' (CostDCNet, MSG_CHN)")
+        if meta == 'plain' and backbone not in ('costdcnet', 'msg_chn'):
+            raise ValueError("meta 'plain' belongs to the CostDCNet and MSG_CHN backbones (NLSPN has 'none')")
         self.emb_dim = 1024 if backbone == 'nlspn' else 512
         if backbone == 'costdcnet' and not max_predict_depth:
             raise ValueError('CostDCNet needs max_predict_depth (the far plane of its cost volume, ExternalModel_Adapt(max_predict_depth))')
@@ -91,7 +93,8 @@ class Engine:
                                   {'2layers': _lib.PTTA_META_2LAYERS, 'none': _lib.PTTA_META_NONE}.get(meta, _lib.PTTA_META_1LAYER) |
                                   (_lib.PTTA_NLSPN_LEGACY_OFFSET if (legacy_offset and backbone == 'nlspn') else 0) |
                                   (_lib.PTTA_SYNCBN_ADAPT if (syncbn_adapted and backbone in ('nlspn', 'costdcnet')) else 0) |
-                                  (_lib.PTTA_COSTDC_PLAIN if meta == 'plain' else 0) |
+                                  (_lib.PTTA_COSTDC_PLAIN if (meta == 'plain' and backbone == 'costdcnet') else 0) |
+                                  (_lib.PTTA_MSGCHN_PLAIN if (meta == 'plain' and backbone == 'msg_chn') else 0) |
                                   (_lib.PTTA_ADAPT_META_ONLY if adapt_mode != 'meta_bn' else 0),
                                   self.n, self.h, self.w, code, byref(self.hp))
         if rc != 0:
@@ -113,7 +116,7 @@ class Engine:
             self.adapted_numel[name] = int(n.value)
             # entries of the reference's parameter list behind this tensor (CostDCNet's DDP list names four tensors twice: include/ptta.h)
             self.adapted_repeat[name] = int(self.lib.ptta_adapted_repeat(self.handle, i))
-        if backbone in ('nlspn', 'costdcnet'):
+        if backbone in ('nlspn', 'costdcnet') or meta == 'plain':
             self.adapted = names
         else:
             assert names == list(self.adapted), (names, self.adapted)

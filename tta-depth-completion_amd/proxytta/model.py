@@ -357,8 +357,9 @@ class MsgChnModel_Adapt(object):
             self._clear_engines()
             return
         self.sync_bn = True
-        for eng in self._engines.values():
-            eng.enable_stat_sync()
+        for key, eng in self._engines.items():
+            if key[0] != 'source':                  # (`_forward` has no BatchNorm: the source engine stays what it is)
+                eng.enable_stat_sync()
 
     def restore_model(self, restore_path, optimizer=None):
         ckpt = torch.load(restore_path, map_location=self.device)
@@ -404,6 +405,23 @@ class MsgChnModel_Adapt(object):
             eng._t = 0
             if self.sync_bn:
                 eng.enable_stat_sync()          # no-op with one rank
+            self._engines[key] = eng
+        return eng
+
+    def _source_engine(self, image):
+        """The engine of `network._forward` (network_exp_msg_chn_adapt.py:418-461), the loaded checkpoint without the meta layer, the zero-image
+        pass and the heads (include/ptta.h PTTA_MSGCHN_PLAIN): built from this model's backbone tensors beside the ProxyTTA engines, on a
+        model that was never prepared too, always fp32 (the scored forward of the mixed mode is the fp32 one already).  Nothing adapts, so it
+        holds no bound parameter: load_state_dict reloads it, _clear_engines drops it with the others."""
+        n, _, h, w = image.shape
+        key = ('source', n, h, w)
+        eng = self._engines.get(key)
+        if eng is None:
+            eng = Engine(n, h, w, dtype='fp32', max_input_depth=self.max_input_depth, meta='plain', **self.hparams)
+            assert eng.adapted == [] and eng.rows == 0, 'the source handle adapts nothing and has no heads'
+            eng.load_state_dict(self.model.state_dict())          # conv1_rgb_meta.*, proj*, pred* of a prepared model: accepted and ignored
+            if getattr(self, '_image_norm', None) is not None:
+                eng.set_image_norm(self._image_norm)
             self._engines[key] = eng
         return eng
 
@@ -454,17 +472,28 @@ class MsgChnModel_Adapt(object):
 
     # ---- forward / loss -----------------------------------------------------------------------
     def forward(self, image, sparse_depth, intrinsics=None, crop_mask=None, loss_type='pretrain'):
-        if 'head' in loss_type and 'init_meta' not in loss_type and loss_type != 'prepare':
+        """network.forward's branches in its own order (network_exp_msg_chn_adapt.py:342-403): 'prepare', 'init_meta', 'head',
+        'meta' + 'selfsup', then 'pretrain' in the string -- `_forward`, the source model, on a prepared model too."""
+        if loss_type == 'prepare' or 'init_meta' in loss_type:
+            raise NotImplementedError('loss_type %r (the stage-1 meta-layer trainer) is not on the accelerated path' % loss_type)
+        if 'head' in loss_type:
             if not self.training:
                 raise NotImplementedError('the head forward is a training-mode call (head_main.py:441)')
             return self.head_forward(image, sparse_depth, loss_type)
-        if not ('meta' in loss_type and 'selfsup' in loss_type):
-            raise NotImplementedError('loss_type %r is not on the accelerated path' % loss_type)
-        if self.training and 'adapt' in loss_type:
-            params = dict(self.model.named_parameters())
-            return self._timed(lambda: _ForwardFn.apply(self, image, sparse_depth, *[params[k] for k in self.adapted]), loss_type)
-        with torch.no_grad():
-            return self._timed(lambda: self._engine(image).forward_eval(image, sparse_depth), loss_type)
+        if 'meta' in loss_type and 'selfsup' in loss_type:
+            if self.training and 'adapt' in loss_type:
+                params = dict(self.model.named_parameters())
+                return self._timed(lambda: _ForwardFn.apply(self, image, sparse_depth, *[params[k] for k in self.adapted]), loss_type)
+            with torch.no_grad():
+                return self._timed(lambda: self._engine(image).forward_eval(image, sparse_depth), loss_type)
+        if 'pretrain' not in loss_type:             # the reference leaves `output` unbound here and raises at its return
+            raise NotImplementedError('loss_type %r matches no branch of the network\'s forward' % loss_type)
+        if self.training:
+            # the reference returns three scales with autograd into EVERY parameter of the network
+            raise NotImplementedError("loss_type %r in training mode: autograd into every parameter is not on the accelerated path "
+                                      "(eval mode runs the source model)" % loss_type)
+        with torch.no_grad():                       # output_d11, the scale the eval wrapper returns (src/msg_chn_model_adapt.py:179-181)
+            return self._timed(lambda: self._source_engine(image).forward_eval(image, sparse_depth), loss_type)
 
     def step(self, image, sparse_depth, validity_map=None, loss_image=None, want_depth=False, next_frame=None):
         """The fused step.  next_frame = (image, sparse_depth) of the frame the NEXT call will pass (the data loader's look-ahead): the part of

@@ -187,6 +187,17 @@ def formula_state_dict(prepare_mode='meta_selfsup_seq_1layer_ema', gain=1.0, hea
     return sd
 
 
+# what _prepare_head adds to the MSG_CHN network: a stage-3 checkpoint holds these keys, the source model (`_forward`,
+# network_exp_msg_chn_adapt.py:418-461) runs none of them and a stage-0 checkpoint has none
+MSG_CHN_STAGE3_ONLY = ('conv1_rgb_meta.', 'proj', 'pred')
+
+
+def formula_state_dict_source(gain=1.0):
+    """The stage-0 form of formula_state_dict: the backbone tensors alone, as ExternalModel_Adapt('msg_chn') holds them before
+    `_prepare_head` (same values as in either stage-3 form: the backbone keys do not depend on the meta layer)."""
+    return {k: v for k, v in formula_state_dict(gain=gain).items() if not k.startswith(MSG_CHN_STAGE3_ONLY)}
+
+
 def synthetic_frame(frame_idx, height, width, n=1, density=0.05, dmin=1.0, dmax=80.0):
     """KITTI-shaped synthetic frame: image U[0,1) (n,3,H,W) and a sparse depth
     map with Bernoulli(density) support and U[dmin,dmax) metres (n,1,H,W), both float32."""
