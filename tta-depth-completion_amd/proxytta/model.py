@@ -7,6 +7,8 @@ restore_model / save_model / convert_syncbn / distributed_data_parallel), so a t
 driver runs unchanged; underneath, forward, loss, backward and Adam are libptta_hip kernels.
 ``step()`` and ``adapt()`` are the fused entry points the reference only has inline
 (src/tta_main.py:579-636 and :504-804).
+``_AdapterBase`` holds what the three per-backbone adapters share (``MsgChnModel_Adapt`` here, proxytta/nlspn.py, proxytta/costdcnet.py);
+what a backbone does differently is an override or a class attribute there.
 """
 import math
 
@@ -14,9 +16,15 @@ import torch
 import torch.nn as nn
 
 from . import _lib, synth
-from .engine import ADAPTED, HEAD_TARGETS, Engine, adapted_names
+from .engine import HEAD_TARGETS, Engine, adapted_names
+from .engine import _BOUND_SUFFIX as _BUFFERS               # the BatchNorm leaves that are buffers, not parameters
 
 CANONICAL_LOSS_TYPE = 'adapt_meta_selfsup_seq_ema_reverse'
+_HEAD_LEAVES = ('proj', 'pred', 'conv1_rgb_meta')           # what _prepare_head adds: the heads (proj_t too) and the meta layer
+
+
+def _unique(names):
+    return list(dict.fromkeys(names))
 
 
 class _Tree(nn.Module):
@@ -87,6 +95,22 @@ class _ForwardFn(torch.autograd.Function):
         return (None, None, None) + tuple(grads)
 
 
+class _PlainForwardFn(torch.autograd.Function):
+    """depth = `_forward`(image, sparse) in training mode on the baseline engine; backward -> gradients of its BatchNorm2d tensors
+    (NLSPN: 86, CostDCNet: 30)."""
+
+    @staticmethod
+    def forward(ctx, eng, image, sparse, *adapted):
+        depth, _, _ = eng.forward_train(image, sparse)
+        ctx.eng = eng
+        ctx.params = dict(zip(eng.adapted, adapted))
+        return depth
+
+    @staticmethod
+    def backward(ctx, g_depth):
+        return (None, None, None) + tuple(ctx.eng.backward_all(g_depth, None, ctx.params))
+
+
 class _LossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, eng, image, depth, sparse, validity, emb, ref, w_sd, w_sm, w_cos):
@@ -120,36 +144,65 @@ class _PrepareLossFn(torch.autograd.Function):
         return (None, None) + tuple(None if g is None else g * g_loss for g in ctx.grads)
 
 
-class MsgChnModel_Adapt(object):
-    """Counterpart of src/msg_chn_model_adapt.py:11-556 on libptta_hip."""
+class _AdapterBase(object):
+    """What the per-backbone adapters share: the parameter tree, the per-shape engines and how they are bound, the plain
+    (no meta layer) engines of the backbones that have a BatchNorm-adaptation baseline, the stage-2 head trainer and the fused step.
+    A backbone states its key table, its Engine keywords (`_new_engine`), its adapted list (`_set_adapted`, `adapt_parameters`)
+    and the routing of its `forward`."""
 
-    def __init__(self, max_predict_depth=5.0, inpainting=False, device=torch.device('cuda'), dtype='fp32',
-                 max_input_depth=None):
+    key_table = None                            # synth.<backbone>_keys: the ordered (key, shape) table of the backbone's state dict
+    _init = staticmethod(_init_tensor)
+    # whether `reverse` leaves proj without a gradient in stage 2.  NLSPN / CostDCNet: ref = proj_t(...), proj trains in both directions (csrc/ghead.hip)
+    heads_reverse_freezes_proj = False
+    syncbn_extends_adapted = True               # convert_syncbn: the heads' (and more) BatchNorm join the adapted list, which is rebuilt
+
+    def __init__(self, max_predict_depth, max_input_depth, device, dtype='fp32'):
         self.max_predict_depth = max_predict_depth
         self.max_input_depth = max_input_depth
         self.device = device
         self.dtype = dtype
         self.training = True
-        self.prepare_mode = None
+        self.prepare_mode = self.meta = None
+        # adapted_listed: the reference's parameter list, duplicates included (None: the backbone names no tensor twice); adapted: the tensors behind it
+        self.adapted = self.adapted_listed = None
+        self.stats_dropped = False        # adapt_parameters('meta_bn') ran: the adapted BatchNorm2d lost their running statistics
         self.model = _Tree()
-        for k, s in synth.msg_chn_keys():                     # heads + meta layer come with _prepare_head
-            if not k.startswith(('rgb_encoder', 'depth_')):
-                continue
-            self.model._leaf(k, _init_tensor(k, s), not k.endswith(('running_mean', 'running_var', 'num_batches_tracked')))
+        for k, s in self._state_keys():
+            if not k.startswith(_HEAD_LEAVES):                # heads + meta layer come with _prepare_head
+                self.model._leaf(k, self._init(k, s), not k.endswith(_BUFFERS))
         self._engines = {}
         self._opt_state = {}
         self._adam_t = 0              # torch.optim.Adam's state['step'], shared by every per-shape engine
+        self._optimizer = None        # bind_optimizer's
+        self._never_stepped = set()   # adapted tensors that torch.optim.Adam would leave without a `step` (CostDCNet under SyncBatchNorm)
+        self._image_norm = None
         self.sync_bn = False
         self.hparams = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                             w_sparse_depth=1.0, w_smoothness=1.0, w_cos=1.0)
         self.total_time = self.train_time = self.eval_time = 0.0
+        # stage 2: set by prepare_parameters / bind_head_optimizer / convert_syncbn / the head calls
+        self._head_names = None
+        self._head_syncbn = False
+        self._head_hp = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, tau=0.999)
+        self._head_opt = None
+        self._head_state = {}
+        self._head_t = 0
+        self._head_mode = self._head_last = None
         self.to(device)
+
+    def _state_keys(self):
+        """(key, shape) of this backbone's tensors under the model's prepare mode (never prepared: the table's default, the 1layer one)."""
+        return self.key_table(self.prepare_mode) if self.prepare_mode else self.key_table()
 
     def _clear_engines(self):
         """Release every per-shape engine (workspaces are GBs at full size: do not wait for __del__)."""
-        engines, self._engines = getattr(self, '_engines', {}), {}
+        engines, self._engines = self._engines, {}
         for eng in engines.values():
             eng.close()
+
+    def _drop_plain_engines(self):
+        for key in [k for k in self._engines if k[0] == 'plain']:
+            self._engines.pop(key).close()
 
     def _timed(self, fn, loss_type):
         """The reference's wall-clock hook: `'time' in loss_type` brackets the network forward with
@@ -172,28 +225,34 @@ class MsgChnModel_Adapt(object):
 
     # ---- reference surface -----------------------------------------------------------------
     def _prepare_head(self, mode=''):
-        """network_adapt._prepare_head (network_exp_msg_chn_adapt.py:1022-1087)."""
-        if 'meta' not in mode or 'selfsup' not in mode or 'ema' not in mode or 'seq' not in mode:
-            raise NotImplementedError('hot path covers prepare_mode meta_selfsup_seq_{1layer}_ema, got %r' % mode)
-        if '1layer' not in mode and '2layers' not in mode:
-            raise NotImplementedError('meta layer of %r is not on the accelerated path (1layer / 2layers are)' % mode)
+        """The network's _prepare_head (network_exp_msg_chn_adapt.py:1022-1087, nlspnmodel_adapt.py:1333-1396, CostDCNet_adapt.py:426-496):
+        proj / proj_t / pred and the meta layer join the tree, the adapted list is the new mode's, the engines made so far are released."""
+        if 'meta' not in mode or 'selfsup' not in mode or 'ema' not in mode or 'seq' not in mode or \
+                ('1layer' not in mode and '2layers' not in mode):
+            raise NotImplementedError('hot path covers prepare_mode meta_selfsup_seq_{1layer,2layers}_ema, got %r' % mode)
         self.prepare_mode = mode
         self.meta = '2layers' if '2layers' in mode else '1layer'
-        self.adapted = adapted_names(self.meta)
-        for k, s in synth.msg_chn_keys(mode):
-            if k.startswith(('proj', 'pred', 'conv1_rgb_meta')):
-                self.model._leaf(k, _init_tensor(k, s).to(self.device),
-                                 not k.endswith(('running_mean', 'running_var', 'num_batches_tracked')))
-        self._clear_engines()
+        for k, s in self._state_keys():
+            if k.startswith(_HEAD_LEAVES):
+                self.model._leaf(k, self._init(k, s).to(self.device), not k.endswith(_BUFFERS))
+        self._set_adapted()
 
     def parameters(self):
         return list(self.model.parameters())
 
-    def adapt_parameters(self, mode=None):
-        """mode 'meta': every parameter whose name contains 'meta' (msg_chn_model_adapt.py:392-396)."""
-        if mode != 'meta':
-            raise NotImplementedError("adapt_mode %r: only 'meta' is on the accelerated path" % mode)
-        return nn.ParameterList([p for n, p in self.model.named_parameters() if 'meta' in n])
+    def _select_baseline(self, listed):
+        """adapt_parameters('meta_bn') on a model whose head was never prepared, the BatchNorm-adaptation baseline: no parameter is called 'meta'
+        yet, so the list is gamma / beta of the backbone's BatchNorm2d alone; forward / step / compute_loss then run on the engine without
+        the meta layer (`_plain_engine`)."""
+        if self.sync_bn:
+            raise NotImplementedError('the BatchNorm-adaptation baseline runs on one rank (no SyncBatchNorm form)')
+        self.adapted_listed, self.adapted = listed, list(listed)
+        self.stats_dropped = True
+        self._clear_engines()
+
+    def _listed_parameters(self):
+        params = dict(self.model.named_parameters())
+        return nn.ParameterList([params[k] for k in self.adapted_listed])
 
     # ---- stage 2 (src/head_main.py:259-276, 464-480) ------------------------------------------------------
     def prepare_parameters(self, mode=''):
@@ -219,13 +278,6 @@ class MsgChnModel_Adapt(object):
         self._head_names = [k for k, _ in self.model.named_parameters() if ('proj' in k or 'pred' in k) and '_t' not in k]
         return [params[k] for k in self._head_names]
 
-    # (key, shape) table of this backbone's state dict and whether `reverse` leaves proj without a gradient (MSG_CHN: its reference branch is
-    # proj itself, network_exp_msg_chn_adapt.py:691-694; NLSPN / CostDCNet: the EMA target proj_t, so proj trains in both directions)
-    heads_reverse_freezes_proj = True
-
-    def _state_keys(self):
-        return synth.msg_chn_keys(self.prepare_mode)
-
     def bind_head_optimizer(self, optimizer, tau=0.999):
         """Share Adam state with a torch.optim.Adam built on prepare_parameters(): `head_step` then updates its exp_avg /
         exp_avg_sq / step in place, so optimizer.state_dict() (save_model) stays meaningful."""
@@ -248,24 +300,21 @@ class MsgChnModel_Adapt(object):
 
     def _head_engine(self, image):
         eng = self._engine(image)
-        if not getattr(eng, '_heads_bound', False):
-            if getattr(self, '_head_names', None) is None:
+        if not eng._heads_bound:
+            if self._head_names is None:
                 raise RuntimeError('prepare_parameters(\'head_selfsup_ema\') must be called before a head forward (head_main.py:268)')
-            if getattr(self, '_head_syncbn', False):
+            if self._head_syncbn:
                 eng.set_head_form(_lib.PTTA_HEAD_FORM_SYNCBN)
             params = dict(self.model.named_parameters())
-            state = getattr(self, '_head_state', None) or {}
             for k in self._head_names:
-                st = state.get(k) or {'exp_avg': torch.zeros_like(params[k].data), 'exp_avg_sq': torch.zeros_like(params[k].data)}
-                state[k] = st
+                st = self._head_state.get(k) or {'exp_avg': torch.zeros_like(params[k].data), 'exp_avg_sq': torch.zeros_like(params[k].data)}
+                self._head_state[k] = st
                 eng.bind_head(k, params[k].data, st['exp_avg'], st['exp_avg_sq'])
-            self._head_state = state
             for k in HEAD_TARGETS:
                 eng.bind_head(k, params[k].data)
-            hp = getattr(self, '_head_hp', None) or dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, tau=0.999)
-            eng.set_head_hparams(adam_step=getattr(self, '_head_t', 0), **hp)
-            eng._head_t = getattr(self, '_head_t', 0)
-            if getattr(self, '_head_syncbn', False):
+            eng.set_head_hparams(adam_step=self._head_t, **self._head_hp)
+            eng._head_t = self._head_t
+            if self._head_syncbn:
                 eng.enable_stat_sync()          # after the binds: its buffer holds the head gradients too (no-op with one rank)
             eng._heads_bound = True
         return eng
@@ -274,15 +323,15 @@ class MsgChnModel_Adapt(object):
         """Counterpart of _sync_adam_step for the stage-2 heads: every (batch, height, width) engine has its own device-side
         step count, torch.optim.Adam has ONE `step` per parameter -- a second engine (the last short batch of a loader) must
         continue the bias correction where the first one stands."""
-        t = getattr(self, '_head_t', 0)
-        if getattr(eng, '_head_t', None) != t:
-            hp = getattr(self, '_head_hp', None) or dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, tau=0.999)
-            eng.set_head_hparams(adam_step=t, **hp)
-            eng._head_t = t
+        if eng._head_t != self._head_t:
+            eng.set_head_hparams(adam_step=self._head_t, **self._head_hp)
+            eng._head_t = self._head_t
 
     def head_forward(self, image, sparse_depth, loss_type):
         """forward(loss_type='head_selfsup_seq_ema[_reverse]') in training mode: (None, embedding, reference)
         (network_exp_msg_chn_adapt.py:610-699); the EMA of proj_t runs first (:682,:691)."""
+        if not self.training:
+            raise NotImplementedError('the head forward is a training-mode call (head_main.py:441)')
         if 'ema' not in loss_type or 'adapt' in loss_type:
             raise NotImplementedError('loss_type %r is not on the accelerated path' % loss_type)
         eng = self._head_engine(image)
@@ -293,7 +342,7 @@ class MsgChnModel_Adapt(object):
 
     def prepare_loss(self, embedding, reference):
         """compute_loss(loss_type='prepare'): the loss of the LAST head forward (embedding / reference are its outputs)."""
-        eng = getattr(self, '_head_last', None)
+        eng = self._head_last
         if eng is None:
             raise RuntimeError('compute_loss(loss_type=\'prepare\') follows a head forward')
         params = dict(self.model.named_parameters())
@@ -306,13 +355,13 @@ class MsgChnModel_Adapt(object):
         # the library keeps ONE step count for the head tensors, torch.optim.Adam one per parameter: in `reverse` mode only
         # `pred` steps, so a run that switches between the two loss types would give proj pred's count -> refused
         rev = 'reverse' in loss_type
-        if self.heads_reverse_freezes_proj and getattr(self, '_head_mode', rev) != rev and getattr(self, '_head_t', 0) > 0:
+        if self.heads_reverse_freezes_proj and self._head_mode not in (None, rev) and self._head_t > 0:
             raise NotImplementedError('head_step: switching between reverse and non-reverse loss types inside one run is not supported '
                                       '(per-parameter Adam step counts would diverge)')
         self._head_mode = rev
         self._sync_head_step(eng)
         loss = eng.head_step(image, sparse_depth, rev)
-        self._head_t = getattr(self, '_head_t', 0) + 1
+        self._head_t += 1
         eng._head_t = self._head_t
         live = self._head_names if (not rev or not self.heads_reverse_freezes_proj) else [k for k in self._head_names if k.startswith('pred')]
         for k in live:
@@ -347,26 +396,31 @@ class MsgChnModel_Adapt(object):
         self.ddp_rank = rank
 
     def convert_syncbn(self, apex=False):
-        """SyncBatchNorm.convert_sync_batchnorm (msg_chn_model_adapt.py:547-556): from now on train-mode BatchNorm
-        statistics are those of the GLOBAL batch.  With one rank that is what the engine computes anyway; with
+        """SyncBatchNorm.convert_sync_batchnorm (msg_chn_model_adapt.py:547-556, costdcnet_model_adapt.py:535-546): from now on train-mode
+        BatchNorm statistics are those of the GLOBAL batch.  With one rank that is what the engine computes anyway; with
         several ranks the statistics are exchanged inside proxytta.distributed.shared_parameter_step.
+        NLSPN / CostDCNet: the reference converts BEFORE adapt_parameters('meta_bn') (src/tta_main.py:326,339), so every BatchNorm of the
+        model passes its isinstance test from here on: the adapted list grows (nlspn_adapted_names / costdcnet_adapted_names, syncbn) and the
+        engines made afterwards are the library's PTTA_SYNCBN_ADAPT ones.
         After prepare_parameters('head_selfsup_ema') this is stage 2 (src/head_main.py:268, then :278): the head engines take the
         SyncBatchNorm form (include/ptta.h ptta_head_set_form) and the TTA adapted list stays what it is."""
-        if getattr(self, '_head_names', None) is not None:
+        if self._head_names is not None:
             self._head_syncbn = True
             self._clear_engines()
             return
         self.sync_bn = True
         for key, eng in self._engines.items():
-            if key[0] != 'source':                  # (`_forward` has no BatchNorm: the source engine stays what it is)
+            if key[0] != 'source':                  # (MSG_CHN's `_forward` has no BatchNorm: the source engine stays what it is)
                 eng.enable_stat_sync()
+        if self.syncbn_extends_adapted and self.prepare_mode is not None:
+            self._set_adapted()                     # heads exist: the list of the DDP run, for the engines made from here on
 
     def restore_model(self, restore_path, optimizer=None):
         ckpt = torch.load(restore_path, map_location=self.device)
         self.load_state_dict(ckpt['net'])
         if optimizer is not None and 'optimizer' in ckpt:
             optimizer.load_state_dict(ckpt['optimizer'])
-            if getattr(self, '_optimizer', None) is optimizer:
+            if self._optimizer is optimizer:
                 self.bind_optimizer(optimizer)      # load_state_dict REPLACED exp_avg / exp_avg_sq / step: rebind them
         return optimizer, ckpt.get('train_step', 0)
 
@@ -386,44 +440,65 @@ class MsgChnModel_Adapt(object):
             eng.load_state_dict(self.model.state_dict())
 
     # ---- engine plumbing --------------------------------------------------------------------
+    def _bind_engine(self, key, eng, state, names=None):
+        """A new engine takes up this model: `state` loaded (BatchNorm buffers are bound by pointer and updated in place), the parameters
+        `names` bound with their Adam moments -- one pair per tensor, shared by every engine of the model -- then the image normalisation,
+        the Adam step count and the SyncBatchNorm exchange, and the engine is kept under `key`.  names None: an engine that adapts nothing
+        (MSG_CHN's source model), which has no step count to carry and no batch statistics to exchange."""
+        eng.load_state_dict(state)
+        if names is not None:
+            params = dict(self.model.named_parameters())
+            for name in names:
+                p = params[name]
+                st = self._opt_state.setdefault(name, {'exp_avg': torch.zeros_like(p.data), 'exp_avg_sq': torch.zeros_like(p.data)})
+                eng.bind_adapted(name, p.data, st['exp_avg'], st['exp_avg_sq'])
+        if self._image_norm is not None:
+            eng.set_image_norm(self._image_norm)
+        if names is not None:
+            eng._t = 0
+            eng._heads_bound = False
+            if self.sync_bn:
+                eng.enable_stat_sync()          # no-op with one rank
+        self._engines[key] = eng
+        return eng
+
     def _engine(self, image):
         n, _, h, w = image.shape
         key = (n, h, w)
         eng = self._engines.get(key)
         if eng is None:
             if self.prepare_mode is None:
+                if self.stats_dropped:             # the baseline model: its only engine is the one without the meta layer
+                    return self._plain_engine(image)
                 raise RuntimeError('_prepare_head(mode) must be called before forward (tta_main.py:322)')
-            eng = Engine(n, h, w, dtype=self.dtype, max_input_depth=self.max_input_depth, meta=self.meta, **self.hparams)
-            eng.load_state_dict(self.model.state_dict())
-            params = dict(self.model.named_parameters())
-            for name in self.adapted:
-                p = params[name]
-                st = self._opt_state.setdefault(name, {'exp_avg': torch.zeros_like(p.data), 'exp_avg_sq': torch.zeros_like(p.data)})
-                eng.bind_adapted(name, p.data, st['exp_avg'], st['exp_avg_sq'])
-            if getattr(self, '_image_norm', None) is not None:
-                eng.set_image_norm(self._image_norm)
-            eng._t = 0
-            if self.sync_bn:
-                eng.enable_stat_sync()          # no-op with one rank
-            self._engines[key] = eng
+            eng = self._new_engine(n, h, w)
+            if self.adapted_listed is not None:
+                assert all(self.adapted_listed.count(k) == max(eng.adapted_repeat[k], 1) for k in eng.adapted), 'listing counts drifted'
+                assert eng.adapted == self.adapted, 'adapted parameter list drifted from the library'
+            self._bind_engine(key, eng, self.model.state_dict(), self.adapted)
         return eng
 
-    def _source_engine(self, image):
-        """The engine of `network._forward` (network_exp_msg_chn_adapt.py:418-461), the loaded checkpoint without the meta layer, the zero-image
-        pass and the heads (include/ptta.h PTTA_MSGCHN_PLAIN): built from this model's backbone tensors beside the ProxyTTA engines, on a
-        model that was never prepared too, always fp32 (the scored forward of the mixed mode is the fp32 one already).  Nothing adapts, so it
-        holds no bound parameter: load_state_dict reloads it, _clear_engines drops it with the others."""
+    def _plain_engine(self, image):
+        """The engine of `_forward`, the network without the meta layer (NLSPN, CostDCNet): the baseline kind once adapt_parameters('meta_bn')
+        dropped the running statistics (batch statistics, gamma / beta of the BatchNorm2d bound to this model's parameters), the source kind
+        before (every BatchNorm from the loaded running statistics, eval forward only).  One per shape, beside the ProxyTTA engines; the
+        meta layer and the heads of a prepared model are not part of it."""
+        if self.sync_bn:
+            raise NotImplementedError("the network without the meta layer runs on one rank (no SyncBatchNorm form of loss_type 'pretrain')")
         n, _, h, w = image.shape
-        key = ('source', n, h, w)
+        key = ('plain', n, h, w)
         eng = self._engines.get(key)
         if eng is None:
-            eng = Engine(n, h, w, dtype='fp32', max_input_depth=self.max_input_depth, meta='plain', **self.hparams)
-            assert eng.adapted == [] and eng.rows == 0, 'the source handle adapts nothing and has no heads'
-            eng.load_state_dict(self.model.state_dict())          # conv1_rgb_meta.*, proj*, pred* of a prepared model: accepted and ignored
-            if getattr(self, '_image_norm', None) is not None:
-                eng.set_image_norm(self._image_norm)
-            self._engines[key] = eng
+            eng = self._new_engine(n, h, w, plain_mode='meta_bn' if self.stats_dropped else 'meta')
+            # the source model adapts nothing; the baseline every BatchNorm2d tensor of this model's list, none twice
+            want = [k for k in self.adapted if 'meta' not in k] if self.stats_dropped else []
+            assert eng.adapted == want and all(eng.adapted_repeat[k] == 1 for k in want), 'adapted parameter list drifted from the library'
+            self._bind_engine(key, eng, self._plain_state(), want)
         return eng
+
+    def _plain_state(self):
+        """The state a plain engine loads."""
+        return self.model.state_dict()
 
     def _sync_adam_step(self, eng):
         """Every (batch, height, width) has its own engine and device-side step counter; torch.optim.Adam has ONE
@@ -471,21 +546,113 @@ class MsgChnModel_Adapt(object):
         self._optimizer = optimizer
 
     # ---- forward / loss -----------------------------------------------------------------------
+    def _forward_tta(self, image, sparse_depth, loss_type):
+        """The ProxyTTA network.  Training mode with 'adapt' in the string: (depth, emb, ref) with autograd edges to the adapted tensors --
+        loss.backward() runs ptta_loss_backward + ptta_backward and fills their .grad (src/tta_main.py:610-632).  Otherwise the eval forward."""
+        if self.training and 'adapt' in loss_type:
+            params = dict(self.model.named_parameters())
+            return self._timed(lambda: _ForwardFn.apply(self, image, sparse_depth, *[params[k] for k in self.adapted]), loss_type)
+        with torch.no_grad():
+            out = self._timed(lambda: self._engine(image).forward_eval(image, sparse_depth), loss_type)
+        return self._fill(out, loss_type)
+
+    def _forward_plain(self, image, sparse_depth, loss_type):
+        """`_forward`, the network without the meta layer (nlspnmodel_adapt.py:792-848, CostDCNet_adapt.py:177-205).  Eval: the depth.  Training
+        with 'bn' in the string: (depth, None, None) with autograd edges to the BatchNorm2d tensors of the baseline.  Training without 'bn':
+        the reference returns a tensor with autograd into EVERY parameter, which is not on the accelerated path."""
+        if self.training:
+            if 'bn' not in loss_type:
+                raise NotImplementedError("loss_type %r in training mode: autograd into every parameter is not on the accelerated path "
+                                          "('bn' in the string: the BatchNorm-adaptation baseline)" % loss_type)
+            self._require_baseline(loss_type)
+            eng = self._plain_engine(image)
+            params = dict(self.model.named_parameters())
+            depth = self._timed(lambda: _PlainForwardFn.apply(eng, image, sparse_depth, *[params[k] for k in eng.adapted]), loss_type)
+            return depth, None, None
+        with torch.no_grad():
+            out = self._timed(lambda: self._plain_engine(image).forward_eval(image, sparse_depth), loss_type)
+        return self._fill(out, loss_type)
+
+    def _fill(self, out, loss_type):
+        """What a backbone does to its eval output on the host (NLSPN fills holes)."""
+        return out
+
+    def step(self, image, sparse_depth, validity_map=None, loss_image=None, want_depth=False, next_frame=None):
+        """The fused step.  next_frame = (image, sparse_depth) of the frame the NEXT call will pass (the data loader's look-ahead): the part of
+        its forward upstream of the adapted layer then runs beside this step (Engine.step / ptta_step_pipelined); same results."""
+        eng = self._engine(image)
+        self._sync_adam_step(eng)
+        if next_frame is not None and (eng.backbone != 'msg_chn' or tuple(next_frame[0].shape) != tuple(image.shape)):
+            next_frame = None                       # other backbones have nothing upstream of their adapted layers; a new shape is a new engine
+        info, depth = eng.step(image, sparse_depth, validity_map, loss_image, want_depth, **({'next_frame': next_frame} if next_frame is not None else {}))
+        self._adam_t += 1
+        eng._t = self._adam_t
+        opt = self._optimizer
+        if opt is not None:
+            never = self._never_stepped
+            skip = {id(p) for k, p in self.model.named_parameters() if k in never} if never else ()
+            for p in opt.param_groups[0]['params']:             # as listed: a tensor named twice is stepped twice
+                if 'step' in opt.state[p] and id(p) not in skip:
+                    opt.state[p]['step'] += 1
+        return info, depth
+
+
+class MsgChnModel_Adapt(_AdapterBase):
+    """Counterpart of src/msg_chn_model_adapt.py:11-556 on libptta_hip."""
+
+    key_table = staticmethod(synth.msg_chn_keys)
+    heads_reverse_freezes_proj = True           # stage 2: the reference branch of `reverse` is proj itself (network_exp_msg_chn_adapt.py:691-694)
+    syncbn_extends_adapted = False              # the adapted list is the meta layer, whatever the BatchNorm modules are: the engines stay
+
+    def __init__(self, max_predict_depth=5.0, inpainting=False, device=torch.device('cuda'), dtype='fp32',
+                 max_input_depth=None):
+        super().__init__(max_predict_depth, max_input_depth, device, dtype)
+
+    def _prepare_head(self, mode=''):
+        if 'meta' not in mode or 'selfsup' not in mode or 'ema' not in mode or 'seq' not in mode:
+            raise NotImplementedError('hot path covers prepare_mode meta_selfsup_seq_{1layer}_ema, got %r' % mode)
+        if '1layer' not in mode and '2layers' not in mode:
+            raise NotImplementedError('meta layer of %r is not on the accelerated path (1layer / 2layers are)' % mode)
+        super()._prepare_head(mode)
+
+    def _set_adapted(self):
+        self.adapted = adapted_names(self.meta)
+        self._clear_engines()
+
+    def adapt_parameters(self, mode=None):
+        """mode 'meta': every parameter whose name contains 'meta' (msg_chn_model_adapt.py:392-396)."""
+        if mode != 'meta':
+            raise NotImplementedError("adapt_mode %r: only 'meta' is on the accelerated path" % mode)
+        return nn.ParameterList([p for n, p in self.model.named_parameters() if 'meta' in n])
+
+    def _new_engine(self, n, h, w, plain_mode=None):
+        """plain_mode: the source engine, always fp32 (the scored forward of the mixed mode is the fp32 one already)."""
+        return Engine(n, h, w, dtype='fp32' if plain_mode else self.dtype, max_input_depth=self.max_input_depth,
+                      meta='plain' if plain_mode else self.meta, **self.hparams)
+
+    def _source_engine(self, image):
+        """The engine of `network._forward` (network_exp_msg_chn_adapt.py:418-461), the loaded checkpoint without the meta layer, the zero-image
+        pass and the heads (include/ptta.h PTTA_MSGCHN_PLAIN): built from this model's backbone tensors beside the ProxyTTA engines, on a
+        model that was never prepared too.  Nothing adapts, so it holds no bound parameter: load_state_dict reloads it, _clear_engines drops
+        it with the others."""
+        n, _, h, w = image.shape
+        key = ('source', n, h, w)
+        eng = self._engines.get(key)
+        if eng is None:
+            eng = self._new_engine(n, h, w, plain_mode='meta')
+            assert eng.adapted == [] and eng.rows == 0, 'the source handle adapts nothing and has no heads'
+            self._bind_engine(key, eng, self.model.state_dict())  # conv1_rgb_meta.*, proj*, pred* of a prepared model: accepted and ignored
+        return eng
+
     def forward(self, image, sparse_depth, intrinsics=None, crop_mask=None, loss_type='pretrain'):
         """network.forward's branches in its own order (network_exp_msg_chn_adapt.py:342-403): 'prepare', 'init_meta', 'head',
         'meta' + 'selfsup', then 'pretrain' in the string -- `_forward`, the source model, on a prepared model too."""
         if loss_type == 'prepare' or 'init_meta' in loss_type:
             raise NotImplementedError('loss_type %r (the stage-1 meta-layer trainer) is not on the accelerated path' % loss_type)
         if 'head' in loss_type:
-            if not self.training:
-                raise NotImplementedError('the head forward is a training-mode call (head_main.py:441)')
             return self.head_forward(image, sparse_depth, loss_type)
         if 'meta' in loss_type and 'selfsup' in loss_type:
-            if self.training and 'adapt' in loss_type:
-                params = dict(self.model.named_parameters())
-                return self._timed(lambda: _ForwardFn.apply(self, image, sparse_depth, *[params[k] for k in self.adapted]), loss_type)
-            with torch.no_grad():
-                return self._timed(lambda: self._engine(image).forward_eval(image, sparse_depth), loss_type)
+            return self._forward_tta(image, sparse_depth, loss_type)
         if 'pretrain' not in loss_type:             # the reference leaves `output` unbound here and raises at its return
             raise NotImplementedError('loss_type %r matches no branch of the network\'s forward' % loss_type)
         if self.training:
@@ -494,25 +661,6 @@ class MsgChnModel_Adapt(object):
                                       "(eval mode runs the source model)" % loss_type)
         with torch.no_grad():                       # output_d11, the scale the eval wrapper returns (src/msg_chn_model_adapt.py:179-181)
             return self._timed(lambda: self._source_engine(image).forward_eval(image, sparse_depth), loss_type)
-
-    def step(self, image, sparse_depth, validity_map=None, loss_image=None, want_depth=False, next_frame=None):
-        """The fused step.  next_frame = (image, sparse_depth) of the frame the NEXT call will pass (the data loader's look-ahead): the part of
-        its forward upstream of the adapted layer then runs beside this step (Engine.step / ptta_step_pipelined); same results."""
-        eng = self._engine(image)
-        self._sync_adam_step(eng)
-        if next_frame is not None and (getattr(eng, 'backbone', 'msg_chn') != 'msg_chn' or tuple(next_frame[0].shape) != tuple(image.shape)):
-            next_frame = None                       # other backbones have nothing upstream of their adapted layers; a new shape is a new engine
-        info, depth = eng.step(image, sparse_depth, validity_map, loss_image, want_depth, **({'next_frame': next_frame} if next_frame is not None else {}))
-        self._adam_t += 1
-        eng._t = self._adam_t
-        opt = getattr(self, '_optimizer', None)
-        if opt is not None:
-            never = getattr(self, '_never_stepped', None)
-            skip = {id(p) for k, p in self.model.named_parameters() if k in never} if never else ()
-            for p in opt.param_groups[0]['params']:             # as listed: a tensor named twice is stepped twice
-                if 'step' in opt.state[p] and id(p) not in skip:
-                    opt.state[p]['step'] += 1
-        return info, depth
 
 
 def eng_is_padded(eng):
@@ -576,13 +724,6 @@ class ExternalModel_Adapt(object):
     def prepare_parameters(self, mode=''):
         return self.model.prepare_parameters(mode)
 
-    # (key, shape) table of this backbone's state dict and whether `reverse` leaves proj without a gradient (MSG_CHN: its reference branch is
-    # proj itself, network_exp_msg_chn_adapt.py:691-694; NLSPN / CostDCNet: the EMA target proj_t, so proj trains in both directions)
-    heads_reverse_freezes_proj = True
-
-    def _state_keys(self):
-        return synth.msg_chn_keys(self.prepare_mode)
-
     def bind_head_optimizer(self, optimizer, tau=0.999):
         self.model.bind_head_optimizer(optimizer, tau)
 
@@ -622,9 +763,7 @@ class ExternalModel_Adapt(object):
 
     def step(self, image, sparse_depth, validity_map=None, loss_image=None, want_depth=False, next_frame=None):
         """One TTA step (src/tta_main.py:610-633) in one library call; returns (loss_info[4], depth).  next_frame: see the adapter's step."""
-        if next_frame is not None and isinstance(self.model, MsgChnModel_Adapt) and type(self.model) is MsgChnModel_Adapt:
-            return self.model.step(image, sparse_depth, validity_map, loss_image, want_depth, next_frame=next_frame)
-        return self.model.step(image, sparse_depth, validity_map, loss_image, want_depth)
+        return self.model.step(image, sparse_depth, validity_map, loss_image, want_depth, next_frame=next_frame)
 
     def adapt(self, image, sparse_depth, inner_iter=1, validity_map=None, loss_image=None, next_frame=None):
         """Per-frame adaptation = inner_iter steps then the scored eval forward

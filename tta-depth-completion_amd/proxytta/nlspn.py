@@ -18,14 +18,10 @@ The eval path's biharmonic hole filling (src/nlspn_model_adapt.py:124-127, skima
 zeros of the clamped output are returned as zeros.
 """
 import torch
-import torch.nn as nn
 
 from . import synth
 from .engine import Engine
-from .costdcnet import _unique
-from .model import MsgChnModel_Adapt, _ForwardFn, _init_tensor, _Tree
-
-_BUFFERS = ('running_mean', 'running_var', 'num_batches_tracked')
+from .model import _BUFFERS, _HEAD_LEAVES, _AdapterBase, _init_tensor, _unique
 
 
 def nlspn_meta_names(keys):
@@ -54,49 +50,18 @@ def is_plain_loss_type(loss_type):
     return 'pretrain' in loss_type or not any(t in loss_type for t in ('adapt', 'selfsup', 'meta', 'head'))
 
 
-class _PlainForwardFn(torch.autograd.Function):
-    """depth = `_forward`(image, sparse) in training mode on the baseline engine; backward -> gradients of the 86 BatchNorm2d tensors."""
-
-    @staticmethod
-    def forward(ctx, eng, image, sparse, *adapted):
-        depth, _, _ = eng.forward_train(image, sparse)
-        ctx.eng = eng
-        ctx.params = dict(zip(eng.adapted, adapted))
-        return depth
-
-    @staticmethod
-    def backward(ctx, g_depth):
-        return (None, None, None) + tuple(ctx.eng.backward_all(g_depth, None, ctx.params))
-
-
-class NlspnModel_Adapt(MsgChnModel_Adapt):
+class NlspnModel_Adapt(_AdapterBase):
     """Counterpart of src/nlspn_model_adapt.py:13-486."""
+
+    key_table = staticmethod(synth.nlspn_keys)
 
     def __init__(self, device=torch.device('cuda'), max_depth=100.0, inpainting=False, use_pretrained=False, dataset_name=None,
                  from_scratch=False, offset=False, max_input_depth=None):
         self.legacy = bool(offset)                            # args.legacy = offset (src/nlspn_model_adapt.py:62)
-        self.max_predict_depth = max_depth
         self.max_depth = max_depth
-        self.max_input_depth = max_input_depth
-        self.device = device
-        self.dtype = 'fp32'
-        self.training = True
-        self.prepare_mode = None
         self.adapt_mode = 'meta_bn'
-        self.stats_dropped = False        # adapt_parameters('meta_bn') ran: every BatchNorm2d lost its running statistics
-        self.model = _Tree()
-        for k, s in synth.nlspn_keys():
-            if k.startswith(('proj', 'pred', 'conv1_rgb_meta')):
-                continue                                      # come with _prepare_head
-            self.model._leaf(k, self._init(k, s), not k.endswith(_BUFFERS))
-        self._engines = {}
-        self._opt_state = {}
-        self._adam_t = 0
-        self.sync_bn = False
-        self.hparams = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, w_sparse_depth=1.0, w_smoothness=1.0, w_cos=1.0)
-        self.total_time = self.train_time = self.eval_time = 0.0
         self.fill_holes = True            # eval forward: biharmonic hole filling like the reference (False: the raw network output)
-        self.to(device)
+        super().__init__(max_depth, max_input_depth, device)
 
     @staticmethod
     def _init(name, shape):
@@ -108,41 +73,16 @@ class NlspnModel_Adapt(MsgChnModel_Adapt):
             return torch.zeros(shape)                         # nlspnmodel_adapt.py:221-222: zero-initialised
         return _init_tensor(name, shape)
 
-    heads_reverse_freezes_proj = False          # stage 2: ref = proj_t(...), proj trains in both directions (csrc/ghead.hip)
-
-    def _state_keys(self):
-        return [(k, s) for k, s in synth.nlspn_keys(self.prepare_mode) if not (k.startswith('enc2d.') and '.downsample.1.' in k)]
-
-    def _prepare_head(self, mode=''):
-        """NLSPNModel_Adapt._prepare_head (nlspnmodel_adapt.py:1333-1396)."""
-        if 'meta' not in mode or 'selfsup' not in mode or 'ema' not in mode or 'seq' not in mode or \
-                ('1layer' not in mode and '2layers' not in mode):
-            raise NotImplementedError('hot path covers prepare_mode meta_selfsup_seq_{1layer,2layers}_ema, got %r' % mode)
-        self.prepare_mode = mode
-        self.meta = '2layers' if '2layers' in mode else '1layer'
-        for k, s in synth.nlspn_keys(mode):
-            if k.startswith(('proj', 'pred', 'conv1_rgb_meta')):
-                self.model._leaf(k, _init_tensor(k, s).to(self.device), not k.endswith(_BUFFERS))
-        self._set_adapted()
-
     def _set_adapted(self):
-        # adapted_listed: the reference's parameter list (2layers names the block's BatchNorm2d twice); adapted: the tensors behind it
-        keys = [k for k, _ in synth.nlspn_keys(self.prepare_mode)]
+        # adapted_listed: the reference's parameter list (2layers names the block's BatchNorm2d twice; SyncBatchNorm: the 94 tensors of the DDP run)
+        keys = [k for k, _ in self._state_keys()]
         self.adapted_listed = nlspn_adapted_names(keys, self.sync_bn) if self.adapt_mode == 'meta_bn' else nlspn_meta_names(keys)
         self.adapted = _unique(self.adapted_listed)
         self._clear_engines()
 
-    def _drop_plain_engines(self):
-        for key in [k for k in self._engines if k[0] == 'plain']:
-            self._engines.pop(key).close()
-
     def convert_syncbn(self, apex=False):
         self._drop_plain_engines()                  # one rank only: `_plain_engine` refuses from here on
         super().convert_syncbn(apex)
-        if getattr(self, '_head_syncbn', False):    # stage 2: the head trainer's SyncBatchNorm form, the TTA list unchanged
-            return
-        if self.prepare_mode is not None:           # heads exist: the adapted list grows to the 94 tensors of the DDP run
-            self._set_adapted()
 
     def adapt_parameters(self, mode=None):
         """src/nlspn_model_adapt.py:287-340.  'meta_bn' (the NLSPN scripts' mode): the meta layer + gamma / beta of every BatchNorm2d, which
@@ -157,18 +97,9 @@ class NlspnModel_Adapt(MsgChnModel_Adapt):
         if self.prepare_mode is None:
             if mode != 'meta_bn':
                 raise RuntimeError('_prepare_head(mode) must be called before adapt_parameters (tta_main.py:322, :339)')
-            # the BatchNorm-adaptation baseline: no parameter is called 'meta' yet, so the list is gamma / beta of every BatchNorm2d (86 tensors);
-            # forward / step / compute_loss then run on the engine without the meta layer (include/ptta.h PTTA_META_NONE)
-            if self.sync_bn:
-                raise NotImplementedError('the BatchNorm-adaptation baseline runs on one rank (no SyncBatchNorm form)')
-            keys = [k for k, _ in synth.nlspn_keys() if not k.startswith(('proj', 'pred', 'conv1_rgb_meta'))]
-            self.adapt_mode = 'meta_bn'
-            self.adapted_listed = nlspn_adapted_names(keys)
-            self.adapted = list(self.adapted_listed)
-            self.stats_dropped = True
-            self._clear_engines()
-            params = dict(self.model.named_parameters())
-            return nn.ParameterList([params[k] for k in self.adapted_listed])
+            # the BatchNorm-adaptation baseline: gamma / beta of every BatchNorm2d (86 tensors), on the engine of include/ptta.h PTTA_META_NONE
+            self._select_baseline(nlspn_adapted_names([k for k, _ in synth.nlspn_keys() if not k.startswith(_HEAD_LEAVES)]))
+            return self._listed_parameters()
         if mode != 'meta_bn' and (self.meta == '2layers' or self.sync_bn):
             raise NotImplementedError("adapt_mode %r runs with the 1layer meta conv on one rank (the 2layers block and the SyncBatchNorm "
                                       "form of this mode are not built)" % mode)
@@ -178,91 +109,25 @@ class NlspnModel_Adapt(MsgChnModel_Adapt):
         if mode == 'meta_bn' and not self.stats_dropped:
             self.stats_dropped = True
             self._drop_plain_engines()             # a source engine made so far normalised with the statistics this call drops
-        params = dict(self.model.named_parameters())
         # 2layers: four tensors listed twice -- torch.optim.Adam steps them twice per step(), as the reference's (torch 1.10.1; with torch >= 2.0
         # on the GPU build the optimizer with foreach=False for the same), and the fused step() does the same on device
-        return nn.ParameterList([params[k] for k in self.adapted_listed])
+        return self._listed_parameters()
 
-    def _engine(self, image):
-        n, _, h, w = image.shape
-        key = (n, h, w)
-        eng = self._engines.get(key)
-        if eng is None:
-            if self.prepare_mode is None:
-                if self.stats_dropped:             # the baseline model: its only engine is the one without the meta layer
-                    return self._plain_engine(image)
-                raise RuntimeError('_prepare_head(mode) must be called before forward (tta_main.py:322)')
-            eng = self._make_engine(key, n, h, w, self.meta, self.adapt_mode)
-        return eng
-
-    def _plain_engine(self, image):
-        """The engine of `_forward`, the network without the meta layer: the baseline kind once adapt_parameters('meta_bn') dropped the running
-        statistics (batch statistics, gamma / beta of every BatchNorm2d bound to this model's parameters), the source kind before."""
-        if self.sync_bn:
-            raise NotImplementedError("the network without the meta layer runs on one rank (no SyncBatchNorm form of loss_type 'pretrain')")
-        n, _, h, w = image.shape
-        key = ('plain', n, h, w)
-        eng = self._engines.get(key)
-        if eng is None:
-            eng = self._make_engine(key, n, h, w, 'none', 'meta_bn' if self.stats_dropped else 'meta')
-        return eng
-
-    def _make_engine(self, key, n, h, w, meta, adapt_mode):
-        eng = Engine(n, h, w, backbone='nlspn', legacy_offset=self.legacy, max_input_depth=self.max_input_depth,
-                     syncbn_adapted=self.sync_bn, meta=meta, adapt_mode=adapt_mode, **self.hparams)
-        if meta == 'none':     # the source model adapts nothing; the baseline every BatchNorm2d tensor of this model's list, none twice
-            want = [k for k in self.adapted if 'meta' not in k] if adapt_mode == 'meta_bn' else []
-            assert eng.adapted == want and all(eng.adapted_repeat[k] == 1 for k in want), 'adapted parameter list drifted from the library'
-        else:
-            assert all(self.adapted_listed.count(k) == max(eng.adapted_repeat[k], 1) for k in eng.adapted), 'listing counts drifted'
-            assert eng.adapted == self.adapted, 'adapted parameter list drifted from the library'
-        eng.load_state_dict(self.model.state_dict())     # the heads' BatchNorm1d buffers are bound and updated in place
-        params = dict(self.model.named_parameters())
-        for name in eng.adapted:
-            p = params[name]
-            st = self._opt_state.setdefault(name, {'exp_avg': torch.zeros_like(p.data), 'exp_avg_sq': torch.zeros_like(p.data)})
-            eng.bind_adapted(name, p.data, st['exp_avg'], st['exp_avg_sq'])
-        if getattr(self, '_image_norm', None) is not None:
-            eng.set_image_norm(self._image_norm)
-        eng._t = 0
-        if self.sync_bn:
-            eng.enable_stat_sync()
-        self._engines[key] = eng
-        return eng
+    def _new_engine(self, n, h, w, plain_mode=None):
+        """plain_mode: the engine without the meta layer (include/ptta.h PTTA_META_NONE) in that adapt mode."""
+        return Engine(n, h, w, backbone='nlspn', legacy_offset=self.legacy, max_input_depth=self.max_input_depth, syncbn_adapted=self.sync_bn,
+                      meta='none' if plain_mode else self.meta, adapt_mode=plain_mode or self.adapt_mode, **self.hparams)
 
     def forward(self, image, sparse_depth, intrinsics=None, crop_mask=None, loss_type='pretrain'):
         if is_plain_loss_type(loss_type):
             return self._forward_plain(image, sparse_depth, loss_type)
         if 'head' in loss_type and 'init_meta' not in loss_type and loss_type != 'prepare':       # stage 2 (src/head_main.py:464-468)
-            if not self.training:
-                raise NotImplementedError('the head forward is a training-mode call (head_main.py:441)')
             return self.head_forward(image, sparse_depth, loss_type)
-        if self.training and 'adapt' in loss_type:
-            # (depth, emb, ref) with autograd edges to the 88 adapted tensors: loss.backward() runs ptta_loss_backward +
-            # ptta_backward and fills their .grad (src/tta_main.py:610-632)
-            params = dict(self.model.named_parameters())
-            return self._timed(lambda: _ForwardFn.apply(self, image, sparse_depth, *[params[k] for k in self.adapted]), loss_type)
-        with torch.no_grad():
-            out = self._timed(lambda: self._engine(image).forward_eval(image, sparse_depth), loss_type)
-        return self._fill(out, loss_type)
+        return self._forward_tta(image, sparse_depth, loss_type)    # training: autograd edges to the 88 adapted tensors
 
-    def _forward_plain(self, image, sparse_depth, loss_type):
-        """`_forward` (nlspnmodel_adapt.py:792-848).  Eval: the depth.  Training with 'bn' in the string: (depth, None, None) with autograd edges
-        to the 86 BatchNorm2d tensors of the baseline.  Training without 'bn': the reference returns a tensor with autograd into EVERY
-        parameter, which is not on the accelerated path."""
-        if self.training:
-            if 'bn' not in loss_type:
-                raise NotImplementedError("loss_type %r in training mode: autograd into every parameter is not on the accelerated path "
-                                          "('bn' in the string: the BatchNorm-adaptation baseline)" % loss_type)
-            if not self.stats_dropped:
-                raise RuntimeError("loss_type %r in training mode follows adapt_parameters('meta_bn') (the BatchNorm-adaptation baseline)" % loss_type)
-            eng = self._plain_engine(image)
-            params = dict(self.model.named_parameters())
-            depth = self._timed(lambda: _PlainForwardFn.apply(eng, image, sparse_depth, *[params[k] for k in eng.adapted]), loss_type)
-            return depth, None, None
-        with torch.no_grad():
-            out = self._timed(lambda: self._plain_engine(image).forward_eval(image, sparse_depth), loss_type)
-        return self._fill(out, loss_type)
+    def _require_baseline(self, loss_type):
+        if not self.stats_dropped:
+            raise RuntimeError("loss_type %r in training mode follows adapt_parameters('meta_bn') (the BatchNorm-adaptation baseline)" % loss_type)
 
     def _fill(self, out, loss_type):
         # Fill in any holes with inpainting (src/nlspn_model_adapt.py:124-127): exact zeros left by the final clamp are filled by
