@@ -386,6 +386,25 @@ int ptta_head_set_form(ptta_handle h, int form);
 int ptta_crop_flip(const float* src, float* dst, int n, int channels, int height, int width, int crop_height, int crop_width,
                    const int32_t* start_y, const int32_t* start_x, const uint8_t* hflip, const uint8_t* vflip, ptta_stream s);
 
+/* Raw-frame ingest on device: the reference's loader arithmetic and crop in one pass over the frames AS DECODED, so that 5 bytes per pixel
+ * cross the host link instead of 16.  image_u8 is N x src_height x src_width x 3 uint8 (a decoded RGB PNG), sparse_u16 / gt_u16 are
+ * N x src_height x src_width 16-bit integers (decoded depth PNGs), all on the device:
+ *   image_out[b,c,y,x]  = (float) image_u8[b, sy+y, sx+x, c]             load_image(normalize=False, 'CHW'): np.asarray(image, np.float32) +
+ *                                                                        np.transpose (src/data_utils.py:150-158, src/datasets.py:399-407)
+ *   sparse_out[b,0,y,x] = (float) sparse_u16[b, sy+y, sx+x] / multiplier load_depth (src/data_utils.py:219-223): one IEEE fp32 division
+ *   validity_out        = sparse_out > 0 ? 1 : 0                         load_depth_with_validity_map (:182-188)
+ *   gt_out, gt_validity_out: the same from gt_u16
+ * and [sy : sy+height, sx : sx+width] is the loader's random / bottom crop (src/datasets.py:83-170): start_y / start_x are int32, device,
+ * per sample (NULL = 0), the caller's draws, clamped into the sample exactly as ptta_crop_flip clamps them.  Outputs are N x 3 x height x
+ * width and N x 1 x height x width fp32.  Each input may be NULL together with its outputs; validity_out and gt_validity_out may be NULL on
+ * their own.  -22 before any launch: an output without its input, an input without its output, no input at all, n < 1, a size < 1,
+ * height > src_height or width > src_width, a multiplier that is not a positive finite number.  Rows of a width that is a multiple of 4
+ * (16-byte-aligned outputs) are written with 16-byte stores; no byte outside the three source arrays is read.  Flips stay with
+ * ptta_crop_flip, behind ptta_outlier_removal as the reference orders them.  Handle-free, one launch, enqueues only. */
+int ptta_ingest_raw(const uint8_t* image_u8, const uint16_t* sparse_u16, const uint16_t* gt_u16, float* image_out, float* sparse_out,
+                    float* validity_out, float* gt_out, float* gt_validity_out, int n, int src_height, int src_width, int height, int width,
+                    const int32_t* start_y, const int32_t* start_x, float multiplier, ptta_stream s);
+
 /* The other augmentations the adapt scripts enable (bash/adapt/adapt_msgchn_vkitti.sh:34-41; applied in every step,
  * src/tta_main.py:595-605).  The reference implements them with torchvision.transforms.functional 0.10.1 (third party, absent
  * from the reference tree: parity unpinned); each call restates torchvision's tensor algorithm.  All handle-free, enqueue only,
