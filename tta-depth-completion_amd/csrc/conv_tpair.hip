@@ -38,20 +38,33 @@
 //   ReLU mask (sign-bit words) and one addend, both read for the halo pixels too, whose SUM output the second layer reads and the owned
 //   pixels still write (the side upsamplings read it); second half masked.  Hi + lo weights take the fp32 form's LDS plan: 45.5 + 18.4 KB.
 // Everything else stays two launches (the data gradients of the all-fp32 mode among them).
-// Registers (gfx950, 256 available at two blocks per CU): <float, 8, ADD> 255 VGPRs, 4 spilled (two 64-bit addresses, stored once in the
-// prologue, two 8-byte scratch reloads per tile: no traffic to speak of), <float, 8> 252, <float, 4, ..> 224 - 242, narrow forward 177 - 202,
-// all without spills; DG <bf16, 4> 254, no spills; DG <bf16, 8> 256 with 35 spilled (144 B of scratch per lane: the 36 registers of mask
-// words and addends held across phase 1) -- that form runs only where a block has one tile (ptta_conv32_tpair_pays).
+// Registers (gfx950, 256 available at two blocks per CU): <float, 8, ADD> 247 VGPRs, <float, 8> 235, <float, 4, ..> 206 - 224, narrow forward
+// 177 - 202, DG <bf16, 4> 236, all without spills; DG <bf16, 8> 256 with 19 spilled (76 B of scratch per lane: mask words and addends
+// held across phase 1) -- that form runs only where a block has one tile (ptta_conv32_tpair_pays).
+// Where a tile's time goes, and what the waits of the tile loop looked like before the LDS-DMA wait became a builtin: DESIGN_LOG.md §19,
+// profiles/tpair_fullres_before.txt / _after.txt (in-kernel stamps: make DIAG=1, tools/diag_tpair.py).
 #include <type_traits>
 #include "ptta_common.h"
 #include "ptta_kernels.h"
 
+// TIMING (make DIAG=1 only): s_memtime stamps around the phases of the tile loop, printed per wave by two blocks of the launch (tools/diag_tpair.py)
+#define TPSTAMP(v) do { if constexpr (TIMING) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); v = t_; } } while (0)
 // DG: the data gradients' form (narrow storage): weights as hi + lo in both layers, no ReLU; the first layer masked by sign-bit words and
 // summed with one addend -- both read on the halo pixels too -- and its SUM is what the second layer reads; the second layer masked
-template <typename T, int TH, bool ADD, bool DG = false>
+template <typename T, int TH, bool ADD, bool DG = false, bool TIMING = false>
 __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Conv32P<T> p2) {
     static_assert(TH == 4 || TH == 8, "tile heights of the two stride-1 kernels");
+    unsigned long long T0 = 0, ts = 0, tn = 0;
+    unsigned dPro = 0, dStage = 0, dW1 = 0, dBar0 = 0, dPh1 = 0, dBar1 = 0, dHalo = 0, dBar2 = 0, dMfma = 0, dEpi = 0, dBar3 = 0;
+    int ntl = 0;
+    // one phase's cycles: since the previous stamp
+    auto lap = [&](unsigned& d) __attribute__((always_inline)) { if constexpr (TIMING) { TPSTAMP(tn); d += (unsigned)(tn - ts); ts = tn; } };
+    TPSTAMP(T0); ts = T0;
     constexpr bool F32 = sizeof(T) == 4, LO = F32 || DG, RELU = !DG;      // LO: a second (lo) weight image per layer
+    // APRE: the second half's skip addends of an output row are requested in FRONT of that row's MFMAs -- row 0's also in front of the next
+    // window's prefetch -- instead of in its epilogue (ptta_common.h epi_add_loads); the fp32 persistent form, where a block walks several
+    // tiles and the epilogue's round trip is on every tile's critical path
+    constexpr bool APRE = F32 && ADD && TH == 8 && !DG;
     static_assert(!DG || (!F32 && !ADD), "the masked / summed first half exists for the narrow data gradients");
     constexpr int STR = Geo<T>::STR, WL = LO ? 18 * 64 * 16 : 0;
     constexpr int PH = TH + 2;                                  // halo rows (row pitch X3_PW = 34)
@@ -117,6 +130,9 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
 #pragma unroll
             for (int k = 0; k < 2; ++k) wh[t][k] = ph[(t * 2 + k) * 64 + lane];
         if constexpr (LO) {
+            // (a copy loop through registers, each of its five turns waiting for its own round trip: 2.5 k of the prologue's 10 k cycles.
+            // The same pieces by LDS-DMA, all in flight at once and covered by the first tile's wait, measured 7.5 k -- and no gain in the
+            // step that the A/B could tell from noise, with the all-fp32 mode slower on two boxes of three: DESIGN_LOG.md §19)
             const uint4* pl = (const uint4*)p2.wpack2;
             for (int idx = tid; idx < WFR; idx += 256) *(uint4*)(wl_lds + idx * 16) = pl[idx];
         } else {
@@ -124,17 +140,22 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
             for (int idx = tid; idx < WFR; idx += 256) *(uint4*)(w1_lds + idx * 16) = p1h[idx];
         }
     }
+    lap(dPro);
 
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         int b, y0, x0;
         tile_coords(tile, b, y0, x0);
         // ---- the window (prefetched) and the first layer's weights -> LDS ----
         if constexpr (W1T) {
+            // (the lane's byte offset from an opaque copy of the lane id: hoisted out of the tile loop the nine 64-bit source addresses were
+            // 18 long-lived registers, spilled, and every piece waited vmcnt(0) for its address's scratch reload in front of its request)
+            int lane16 = lane * 16;
+            asm volatile("" : "+v"(lane16));
 #pragma unroll
             for (int k = 0; k < (NPC + 3) / 4; ++k) {
                 const int piece = wave + 4 * k;                      // wave-uniform
                 if (piece < NPC) {
-                    const unsigned char* src = (const unsigned char*)(piece < 18 ? p1.wpack : p1.wpack2) + ((size_t)(piece < 18 ? piece : piece - 18) * 64 + lane) * 16;
+                    const unsigned char* src = (const unsigned char*)(piece < 18 ? p1.wpack : p1.wpack2) + (size_t)(piece < 18 ? piece : piece - 18) * 1024 + lane16;
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                      (__attribute__((address_space(3))) void*)(w1_lds + piece * 1024), 16, 0, 0);
                 }
@@ -148,6 +169,7 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
             if (!((vok >> it) & 1u)) x = px_zero<T>();
             if (pix < NWP) px_stage<RELU>(x, win + pix * STR + 16 * (idx & 3), Geo<T>::LO);
         }
+        lap(dStage);
         // DG: the first layer's mask words and addend of this lane's pixels of its groups (halo pixels included; clamped addresses), four
         // channels each -- requested in front of the wait below
         uint32_t mw1[DG ? NGC : 1][4];
@@ -168,8 +190,14 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
                 }
             }
         }
-        if constexpr (W1T) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the weight pieces have landed
+        // the weight pieces have landed.  The wait is the BUILTIN, which the compiler's own wait-count bookkeeping reads: behind a wait
+        // written as inline assembly it still held the LDS-DMA for outstanding and put s_waitcnt vmcnt(0) in front of every later LDS
+        // access of the region -- in front of phase 2's first fragment read (the next window's prefetch, just requested), of the second
+        // row's (the first row's stores) and of the halo tile's writes (the sign-bit stores): every memory round trip of a tile exposed
+        if constexpr (W1T) __builtin_amdgcn_s_waitcnt(0x0F70);                       // vmcnt(0), expcnt and lgkmcnt left alone (gfx9 encoding)
+        lap(dW1);
         lds_barrier();
+        lap(dBar0);
 
         // ---- phase 1: the transposed convolution on the tile and its halo, NGC groups of 32 same-class pixels per wave ----
         const bool wbits = F32 && p1.epi.bits_out != nullptr && b < p1.epi.bits_nb;      // wave-uniform
@@ -274,7 +302,9 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
                 }
             }
         }
+        lap(dPh1);
         lds_barrier();                                            // every wave is done with the window and the weights: the region becomes the halo tile
+        lap(dBar1);
 #pragma unroll
         for (int s_ = 0; s_ < NGC; ++s_) {
             const int code = (int)((sched >> (4 * s_)) & 15u);
@@ -293,13 +323,24 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
                 }
             }
         }
-        if (tile + gridDim.x < ntiles) issue_loads(tile + gridDim.x);      // the next tile's window flies during the second convolution
+        // the next tile's window flies during the second convolution.  APRE: behind row 0's addends, and UNCONDITIONAL (a block's last tile
+        // fetches its own window again, from L2) -- behind a conditional prefetch the wait for the addends would have to be vmcnt(0)
+        float4 ad[APRE ? 8 : 1];
+        if constexpr (APRE) {
+            epi_add_loads(p2.epi, b, y0 + 2 * wave, H, W, i, x0, h, ad);
+            issue_loads(tile + gridDim.x < ntiles ? tile + gridDim.x : tile);
+        } else {
+            if (tile + gridDim.x < ntiles) issue_loads(tile + gridDim.x);
+        }
+        lap(dHalo);
         lds_barrier();
+        lap(dBar2);
 
         // ---- phase 2: the body of the stride-1 kernel on the LDS tile, TH / 4 output rows per wave ----
         auto do_row = [&](const int row) __attribute__((always_inline)) {
             const int y = y0 + row;
             if (y >= H) return;                                   // wave-uniform
+            if constexpr (APRE) { if (row & 1) epi_add_loads(p2.epi, b, y, H, W, i, x0, h, ad); }       // (row 0's: in front of the prefetch, above)
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -332,15 +373,36 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            epi_tile<T, false, DG, ADD>(p2.epi, b, y, H, W, i, acc, x0, h, W, 1, 0, sy, sx, nullptr, 0, 0, &bias2);
+            if constexpr (APRE) {
+                // (the addends are first USED here: left visible, their sum is computed in front of the MFMAs -- eight registers fewer -- and
+                // the row waits for the round trip before its matrix work instead of behind it)
+#pragma unroll
+                for (int g = 0; g < 8; ++g) asm volatile("" : "+v"(ad[g].x), "+v"(ad[g].y), "+v"(ad[g].z), "+v"(ad[g].w));
+            }
+            lap(dMfma);
+            epi_tile<T, false, DG, ADD>(p2.epi, b, y, H, W, i, acc, x0, h, W, 1, 0, sy, sx, nullptr, 0, 0, &bias2, nullptr, APRE ? ad : nullptr);
+            lap(dEpi);
         };
-        if constexpr (TH == 8) {
+        if constexpr (APRE) {
+            // (the two rows as straight-line code: inside a loop the wait-count bookkeeping merges with the back edge and the wait for row 0's
+            // addends becomes vmcnt(0), that is for the prefetch issued behind them -- conv32_s1_x3_kernel's masked variants)
+            do_row(2 * wave); do_row(2 * wave + 1);
+        } else if constexpr (TH == 8) {
 #pragma unroll 1
             for (int rr = 0; rr < 2; ++rr) do_row(2 * wave + rr);
         } else {
             do_row(wave);
         }
         lds_barrier();          // LDS reuse by the next tile's window only: this tile's stores and the prefetch stay in flight
+        lap(dBar3);
+        ++ntl;
+    }
+    if constexpr (TIMING) {
+        TPSTAMP(tn);
+        if ((blockIdx.x == 102 || blockIdx.x == 307) && lane == 0 && ntl > 0)
+            printf("tpair blk %d wave %d tiles %d: life %llu pro %u | per tile: stage %u w1wait %u bar0 %u phase1 %u bar1 %u halo+issue %u bar2 %u mfma2 %u epilogue2 %u bar3 %u\n",
+                   (int)blockIdx.x, wave, ntl, tn - T0, dPro, dStage / ntl, dW1 / ntl, dBar0 / ntl, dPh1 / ntl, dBar1 / ntl, dHalo / ntl, dBar2 / ntl,
+                   dMfma / ntl, dEpi / ntl, dBar3 / ntl);
     }
 }
 
@@ -379,6 +441,15 @@ static int launch_tpair_t(const Conv32Args& f, const Conv32Args& g, int form, in
             return 0;
         }
     }
+#ifdef PTTA_DIAG_STAMPS      // diagnostic build (make DIAG=1): in-kernel phase stamps of the fp32 persistent form with addends
+    if constexpr (sizeof(T) == 4) {
+        if (form == 2 && g.add1) {
+            hipLaunchKernelGGL((conv32_tpair_kernel<T, 8, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, p1, p2);
+            PTTA_CHECK_LAUNCH();
+            return 0;
+        }
+    }
+#endif
 #define KT_(TH_, A_) hipLaunchKernelGGL((conv32_tpair_kernel<T, TH_, A_>), dim3((unsigned)blocks), dim3(256), 0, s, p1, p2)
     if (form == 2) { if (g.add1) KT_(8, true); else KT_(8, false); }
     else { if (g.add1) KT_(4, true); else KT_(4, false); }

@@ -169,11 +169,26 @@ __device__ __forceinline__ void epi_mask_words(const Epi<T>& e, int b, int y, in
 #pragma unroll
     for (int g = 0; g < 4; ++g) mw[g] = mb[min(x0 + (ch & 3) + 8 * g + 4 * h, W - 1)];
 }
+// The skip addends epi_tile's fp32 branch reads for output row y (stride-1 geometry), loaded AHEAD by the caller and passed back as
+// `add_pre` ([0 .. 3] add1, [4 .. 7] add2 when there is one): the same values from the same (clamped) addresses, summed in the same order.
+// Loaded in the epilogue they queue behind the next tile's prefetch and the previous row's stores (vmcnt is in order) and the row's
+// stores wait for a full memory round trip that nothing hides; issued in front of the row's MFMAs they land while the matrix cores work.
+__device__ __forceinline__ void epi_add_loads(const Epi<float>& e, int b, int y, int H, int W, int ch, int x0, int h, float4 (&ad)[8]) {
+    const size_t rowoff = (size_t)min(y, H - 1) * W;
+    const float* a1 = e.add1 + (size_t)(b % e.add1_nb) * H * W * 32;
+    const float* a2 = (e.add2 ? e.add2 : e.add1) + (size_t)(b % (e.add2 ? e.add2_nb : e.add1_nb)) * H * W * 32;      // (no second addend: the values are not used)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const size_t xq = ((size_t)min(x0 + (ch & 3) + 8 * g + 4 * h, W - 1) + rowoff) * 32 + (ch >> 2) * 4;
+        ad[g] = *(const float4*)(a1 + xq);
+        ad[4 + g] = *(const float4*)(a2 + xq);
+    }
+}
 template <typename T, bool UP, bool MASK, bool ADD, bool UPL = false, int UPLW = 18>
 __device__ __forceinline__ void epi_tile(const Epi<T>& e, int b, int y, int H, int W, int ch, const f32x16& acc,
                                          int x0, int h, int Wt, int xstep, int xoff, float sy, float sx,
                                          const void* upw_ = nullptr, int uy0 = 0, int ux0 = 0, const float* bias_lane = nullptr,
-                                         const uint32_t* mw_pre = nullptr) {
+                                         const uint32_t* mw_pre = nullptr, const float4* add_pre = nullptr) {
     const float* upw = (const float*)upw_;                // fp32 storage: the bilinear window holds floats; narrow storage casts upw_ to bf16 below
     const float* bp = e.bias ? e.bias : kZeroBias;       // pointer select, not a branch around the load
     // bias_lane: the lane's bias, loaded ONCE by the kernel (epi_bias).  Loaded here -- once per output row -- it cannot be hoisted by hipcc
@@ -256,11 +271,11 @@ __device__ __forceinline__ void epi_tile(const Epi<T>& e, int b, int y, int H, i
         if (ADD) {
             const float* a1 = (const float*)e.add1 + (size_t)(b % e.add1_nb) * H * W * 32;
 #pragma unroll
-            for (int g = 0; g < 4; ++g) t1[g] = *(const float4*)(a1 + xq[g]);
+            for (int g = 0; g < 4; ++g) t1[g] = add_pre ? add_pre[g] : *(const float4*)(a1 + xq[g]);
             if (e.add2) {
                 const float* a2 = (const float*)e.add2 + (size_t)(b % e.add2_nb) * H * W * 32;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) t2[g] = *(const float4*)(a2 + xq[g]);
+                for (int g = 0; g < 4; ++g) t2[g] = add_pre ? add_pre[4 + g] : *(const float4*)(a2 + xq[g]);
 #pragma unroll
                 for (int g = 0; g < 4; ++g) { t1[g].x += t2[g].x; t1[g].y += t2[g].y; t1[g].z += t2[g].z; t1[g].w += t2[g].w; }
             }
