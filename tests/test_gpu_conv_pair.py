@@ -154,6 +154,73 @@ def test_forms_that_are_not_instantiated_take_the_two_launches():
         _same(ref, got, cs)
 
 
+_MID_CACHE = {}
+
+
+def _two_launch_inputs(b, hm, wm):
+    """The operands of one intermediate size (two addends and a skip map, of which a case passes the ones it wants), shared by its twelve cases."""
+    if (b, hm, wm) not in _MID_CACHE:
+        _MID_CACHE[(b, hm, wm)] = _operands(2 * hm, 2 * wm, hm, wm, b, b, 2, True, seed=hm * 1000 + wm)
+    return _MID_CACHE[(b, hm, wm)]
+
+
+def _skip_ref(up, hm, wm):
+    """float64 bilinear skip of the stride-1 epilogue, [b, hm >> 1, wm >> 1, 32] -> [b, hm, wm, 32]: oracle.msgchn_arith.up2_ref on an even
+    map; an odd one (9 x 13 from 4 x 6) takes the same align-corners weights src = dst (n_in - 1) / (n_out - 1) in exact rationals, which
+    is what the kernels' up_scale(n_in, n_out) rounds to fp32."""
+    from oracle import msgchn_arith as A
+    if hm % 2 == 0 and wm % 2 == 0:
+        return A.up2_ref(up)[0]
+
+    def matrix(n_in, n_out):
+        U = np.zeros((n_out, n_in))
+        for d in range(n_out):
+            num, den = d * (n_in - 1), n_out - 1
+            i0 = min(num // den, n_in - 1)
+            frac = (num - i0 * den) / den
+            U[d, i0] += 1.0 - frac
+            U[d, min(i0 + 1, n_in - 1)] += frac
+        return U
+    return A._sandwich(matrix(hm // 2, hm), up, matrix(wm // 2, wm))
+
+
+# second term of the bound below: eight fp32 roundings (the interpolation's products and sums, the three additions), 8 x 2^-24
+STRIDE1_EPILOGUE_ROUNDINGS = 2.0 ** -21
+
+
+@pytest.mark.parametrize('size', [(1, 9, 13), (2, 72, 480)], ids=['small_kernel_1x9x13', 'x3_kernel_2x72x480'])
+@pytest.mark.parametrize('nadd', [0, 1, 2])
+@pytest.mark.parametrize('up', [0, 1])
+@pytest.mark.parametrize('relu2', [0, 1])
+def test_two_launch_stride1_epilogue_forms(relu2, up, nadd, size):
+    """The second launch of the two-launch chain against float64, on both sides of the small-map rule: 1x9x13 is one partial 4x32 tile
+    (conv32_s1_small_kernel), 2x72x480 is 2 * 15 * 9 = 270 tiles of 8x32, more than 256 (conv32_s1_x3_kernel).  The reference starts from the
+    hook's own first-layer map, so only the second launch is judged:
+        conv(relu2 ? relu(mid) : mid, w2) + b2 [+ up2(up)] [+ a1] [+ a2]
+    within TOL['x3'] * (|x| (*) |w| + |b|) (tests/test_gpu_parity.py _conv_bound) + 2^-21 * (|conv| + |up2| + |a1| + |a2|)."""
+    from tests.gconv_cases import TOL
+    from tests.test_gpu_parity import _conv_bound
+    from tests.util import assert_elementwise
+    b, hm, wm = size
+    x, w1, b1, w2, b2, upm, a1, a2 = _two_launch_inputs(b, hm, wm)
+    upm, a1, a2 = upm if up else None, a1 if nadd >= 1 else None, a2 if nadd >= 2 else None
+    got, did = _pair(x, w1, b1, w2, b2, upm, a1, a2, hm, wm, b, b, S2, True, bool(relu2), 'fp32', False, fused=0)
+    assert did == 0
+    conv, bound = _conv_bound(got['mid'].cpu(), w2.cpu(), b2.cpu(), 0, bool(relu2), TOL['x3'])
+    ref, mag = conv.numpy(), conv.abs().numpy()
+    if up:
+        u = _skip_ref(upm.cpu().numpy(), hm, wm)
+        ref, mag = ref + u, mag + np.abs(u)
+    what = 'two-launch stride-1 relu2=%d up=%d nadd=%d %s' % (relu2, up, nadd, size)
+    assert_elementwise(got['raw'], ref, bound.numpy() + STRIDE1_EPILOGUE_ROUNDINGS * mag, what + ' out_raw')
+    if nadd:
+        for a in (a1, a2)[:nadd]:
+            ref, mag = ref + a.cpu().double().numpy(), mag + a.cpu().double().abs().numpy()
+        assert_elementwise(got['sum'], ref, bound.numpy() + STRIDE1_EPILOGUE_ROUNDINGS * mag, what + ' out_sum')
+    else:
+        assert got['sum'] is None
+
+
 def _frames(n, h, w, k=3):
     return [[torch.from_numpy(x).cuda() for x in synth.synthetic_frame(40 + i, h, w, n)] for i in range(k)]
 

@@ -1,6 +1,6 @@
 // A strided 32 -> 32 convolution and the stride-1 32 -> 32 convolution that consumes it, on SMALL maps, in ONE launch.
 //
-// On the 1/4 ... 1/16-resolution maps every convolution launch is one tile per block and its duration is a latency chain (conv32.hip
+// On the 1/4 ... 1/16-resolution maps every convolution launch is one tile per block and its duration is a latency chain (conv32_s1.hip
 // conv32_s1_small_kernel), so a (stride-2 -> stride-1) pair costs two such chains and a store -> load round trip of the map in between.
 // Here a block owns a 4 x 32 tile of the STRIDE-1 output, the tile grid of conv32_s1_small_kernel: phase 1 computes the first convolution for
 // the tile plus its one-pixel halo (6 x 34 intermediate pixels = seven groups of 32 pixels in row-major order, one per wave) from a
@@ -31,8 +31,7 @@
 //   The first layer's mask words and addend are read for the halo pixels too; its map (when wanted) and its sum are written from the
 //   owned pixels.
 // Not instantiated: a transposed first half (either direction), the data gradients of the all-fp32 mode, every other epilogue combination.
-#include "ptta_common.h"
-#include "ptta_kernels.h"
+#include "conv32_launch.h"
 
 #define PR_TH 4                         // output rows of a tile
 #define PR_TW 32                        // output columns of a tile
@@ -278,26 +277,10 @@ __global__ __launch_bounds__(PR_NT, 1) void conv32_pair_small_kernel(Conv32P<T> 
 }
 
 template <typename T>
-static Conv32P<T> pair_params(const Conv32Args& a, int Hout, int Wout) {
-    Conv32P<T> p;
-    p.in = (const T*)a.in; p.in_nb = a.in_nb > 0 ? a.in_nb : 1;
-    p.wpack = a.w->mbf16; p.wpack2 = (sizeof(T) == 4 || a.w2) ? a.w->mlo : nullptr;
-    p.epi.bias = a.bias;
-    p.epi.up = (const T*)a.up; p.epi.up_nb = a.up_nb > 0 ? a.up_nb : 1;
-    p.epi.mask = (const T*)a.mask; p.epi.mask_nb = a.mask_nb > 0 ? a.mask_nb : 1;
-    p.epi.add1 = (const T*)a.add1; p.epi.add1_nb = a.add1_nb > 0 ? a.add1_nb : 1;
-    p.epi.add2 = (const T*)a.add2; p.epi.add2_nb = a.add2_nb > 0 ? a.add2_nb : 1;
-    p.epi.out_raw = (T*)a.out_raw; p.epi.out_sum = (T*)a.out_sum;
-    p.epi.mask_bits = a.mask_bits; p.epi.bits_out = a.bits_out; p.epi.bits_nb = a.bits_nb; p.epi.bits_sum = a.bits_sum;
-    p.B = a.B; p.Hin = a.Hin; p.Win = a.Win; p.Hout = Hout; p.Wout = Wout;
-    return p;
-}
-
-template <typename T>
 static int launch_pair_t(const Conv32Args& f, const Conv32Args& g, hipStream_t s) {
     const int Hm = f.Hin / 2, Wm = f.Win / 2;
-    const Conv32P<T> p1 = pair_params<T>(f, Hm, Wm), p2 = pair_params<T>(g, Hm, Wm);
-    const long tiles = (long)f.B * ((Wm + PR_TW - 1) / PR_TW) * ((Hm + PR_TH - 1) / PR_TH);
+    const Conv32P<T> p1 = conv32_params<T>(f, Hm, Wm), p2 = conv32_params<T>(g, Hm, Wm);
+    const long tiles = conv32_tiles(f.B, Hm, Wm, PR_TH);
     if constexpr (sizeof(T) == 2) {
         if (f.w2) {            // the data gradients' form
             hipLaunchKernelGGL((conv32_pair_small_kernel<T, CONV_S2, true, false, true, true, false, false, true>), dim3((unsigned)tiles), dim3(PR_NT), 0, s, p1, p2);
@@ -305,8 +288,9 @@ static int launch_pair_t(const Conv32Args& f, const Conv32Args& g, hipStream_t s
             return 0;
         }
     }
-    if (g.add1) hipLaunchKernelGGL((conv32_pair_small_kernel<T, CONV_S2, false, true, false, false, true, true, false>), dim3((unsigned)tiles), dim3(PR_NT), 0, s, p1, p2);
-    else hipLaunchKernelGGL((conv32_pair_small_kernel<T, CONV_S2, false, true, false, false, true, false, false>), dim3((unsigned)tiles), dim3(PR_NT), 0, s, p1, p2);
+    with_flag(g.add1 != nullptr, [&](auto ADD) {
+        hipLaunchKernelGGL((conv32_pair_small_kernel<T, CONV_S2, false, true, false, false, true, decltype(ADD)::value, false>), dim3((unsigned)tiles), dim3(PR_NT), 0, s, p1, p2);
+    });
     PTTA_CHECK_LAUNCH();
     return 0;
 }
@@ -316,24 +300,11 @@ static int launch_pair_t(const Conv32Args& f, const Conv32Args& g, hipStream_t s
 // small-map kernel; the launch returns 1 when it does not (the caller then issues the two launches).
 bool ptta_conv32_pair_applies(const Conv32Args& first, const Conv32Args& second) {
     const Conv32Args &f = first, &g = second;
-    if (!f.w || !g.w || !f.in) return false;
-    if (f.mode != CONV_S2 || g.mode != CONV_S1 || f.bf16 != g.bf16 || f.naive || g.naive || (!f.bf16 && (!f.x3 || !g.x3)) || f.w2 != g.w2) return false;
-    if (f.bits_out && (f.bits_sum || f.bf16)) return false;
-    if (g.bits_out && g.bf16) return false;
-    if (f.w2) {
-        // the data gradients (narrow maps, hi + lo weights, no ReLU): first = mask . conv, sum = that + one addend; second reads the SUM, masked
-        if (!f.bf16 || f.relu_in || g.relu_in || f.up || g.up || f.bits_out || g.bits_out) return false;
-        if (!f.mask || !f.mask_bits || !f.add1 || f.add2 || !f.out_sum) return false;
-        if (!g.mask || !g.mask_bits || g.add1 || g.add2 || g.out_sum || !g.out_raw) return false;
-    } else {
-        // the forward: ReLU on both inputs, first without epilogue operands, second with the bilinear skip and up to two addends
-        if (!f.relu_in || f.up || f.mask || f.add1 || f.add2 || f.out_sum || f.mask_bits) return false;
-        if (!g.relu_in || !g.up || g.mask || g.mask_bits || (g.add2 && !g.add1) || (!g.out_raw && !g.out_sum)) return false;
-    }
+    if (f.mode != CONV_S2 || !conv32_pair_common(f, g)) return false;
+    if (!f.w2 && !g.up) return false;                        // the forward's second half: with the bilinear skip
     const int Hm = f.Hin / 2, Wm = f.Win / 2;
     if (Hm < 2 || Wm < 2 || g.Hin != Hm || g.Win != Wm || g.B != f.B || f.B < 1) return false;
-    const long tiles8 = (long)g.B * ((Wm + 31) / 32) * ((Hm + X3_TH - 1) / X3_TH);
-    return tiles8 <= 256;                                    // (the rule of conv32.hip launch_x3: larger maps keep the persistent kernels)
+    return conv32_s1_small_map(g.B, Hm, Wm);                 // (larger maps keep the persistent kernels)
 }
 int ptta_launch_conv32_pair(const Conv32Args& first, const Conv32Args& second, hipStream_t s) {
     if (!ptta_conv32_pair_applies(first, second)) return 1;

@@ -19,7 +19,7 @@
 // LDS: the window (and, fp32 storage, the first layer's 36 KB of hi + lo fragments) is dead once phase 1's accumulators are complete, the
 // halo tile is not written before that, so the two share one region (results wait in registers across one barrier): fp32 storage 52.4 KB +
 // the second layer's lo fragments 18.4 KB = 70.8 KB (the stride-1 kernel: 67.4 KB), narrow 27.2 + 18.4 KB -- two blocks per CU as
-// before (conv32.hip, the note above conv32_direct_x3_kernel: a form that does not fit beside what runs next to it loses in the step).
+// before (conv32_strided.hip, the note above conv32_direct_x3_kernel: a form that does not fit beside what runs next to it loses in the step).
 // The fp32 form fetches the first layer's fragments again for every tile, from L2 straight into LDS, and waits for them -- and so for the
 // previous tile's stores, vmcnt is in order -- at the top of the tile.  Measured against it in the step (MI355X, full-resolution pair,
 // launch by launch): the same fragments prefetched into 36 registers with the next window, in front of the tile's stores, 95.7 against
@@ -43,12 +43,9 @@
 // held across phase 1) -- that form runs only where a block has one tile (ptta_conv32_tpair_pays).
 // Where a tile's time goes, and what the waits of the tile loop looked like before the LDS-DMA wait became a builtin: DESIGN_LOG.md §19,
 // profiles/tpair_fullres_before.txt / _after.txt (in-kernel stamps: make DIAG=1, tools/diag_tpair.py).
-#include <type_traits>
-#include "ptta_common.h"
-#include "ptta_kernels.h"
+#include "conv32_launch.h"
 
 // TIMING (make DIAG=1 only): s_memtime stamps around the phases of the tile loop, printed per wave by two blocks of the launch (tools/diag_tpair.py)
-#define TPSTAMP(v) do { if constexpr (TIMING) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); v = t_; } } while (0)
 // DG: the data gradients' form (narrow storage): weights as hi + lo in both layers, no ReLU; the first layer masked by sign-bit words and
 // summed with one addend -- both read on the halo pixels too -- and its SUM is what the second layer reads; the second layer masked
 template <typename T, int TH, bool ADD, bool DG = false, bool TIMING = false>
@@ -58,8 +55,8 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
     unsigned dPro = 0, dStage = 0, dW1 = 0, dBar0 = 0, dPh1 = 0, dBar1 = 0, dHalo = 0, dBar2 = 0, dMfma = 0, dEpi = 0, dBar3 = 0;
     int ntl = 0;
     // one phase's cycles: since the previous stamp
-    auto lap = [&](unsigned& d) __attribute__((always_inline)) { if constexpr (TIMING) { TPSTAMP(tn); d += (unsigned)(tn - ts); ts = tn; } };
-    TPSTAMP(T0); ts = T0;
+    auto lap = [&](unsigned& d) __attribute__((always_inline)) { if constexpr (TIMING) { PTTA_STAMP(tn); d += (unsigned)(tn - ts); ts = tn; } };
+    PTTA_STAMP(T0); ts = T0;
     constexpr bool F32 = sizeof(T) == 4, LO = F32 || DG, RELU = !DG;      // LO: a second (lo) weight image per layer
     // APRE: the second half's skip addends of an output row are requested in FRONT of that row's MFMAs -- row 0's also in front of the next
     // window's prefetch -- instead of in its epilogue (ptta_common.h epi_add_loads); the fp32 persistent form, where a block walks several
@@ -97,18 +94,12 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
     const unsigned sched = TH == 8 ? (wave == 0 ? 0x04Cu : wave == 1 ? 0x18Du : wave == 2 ? 0x25Eu : 0x6A9u)
                                    : (wave == 0 ? 0x0Cu : wave == 1 ? 0x1Du : wave == 2 ? 0x54u : 0x98u);
 
-    auto tile_coords = [&](long tile, int& b, int& y0, int& x0) {
-        long t_ = tile;
-        const int ty = (int)(t_ % nty); t_ /= nty;          // y fastest: neighbouring blocks share window rows in L2
-        const int tx = (int)(t_ % ntx);
-        b = (int)(t_ / ntx); y0 = ty * TH; x0 = tx << 5;
-    };
     // the window's loads are UNCONDITIONAL (clamped address); zero outside the map when the values go to LDS one tile later
     Px<T> v[NIT];
     unsigned vok = 0;
     auto issue_loads = [&](long tile) {
         int b, y0, x0;
-        tile_coords(tile, b, y0, x0);
+        tile_coords<TH>(tile, ntx, nty, b, y0, x0);
         const T* inb = p1.in + (size_t)(b % p1.in_nb) * Hin * Win * 32;
         vok = 0;
 #pragma unroll
@@ -144,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
 
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         int b, y0, x0;
-        tile_coords(tile, b, y0, x0);
+        tile_coords<TH>(tile, ntx, nty, b, y0, x0);
         // ---- the window (prefetched) and the first layer's weights -> LDS ----
         if constexpr (W1T) {
             // (the lane's byte offset from an opaque copy of the lane id: hoisted out of the tile loop the nine 64-bit source addresses were
@@ -398,7 +389,7 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
         ++ntl;
     }
     if constexpr (TIMING) {
-        TPSTAMP(tn);
+        PTTA_STAMP(tn);
         if ((blockIdx.x == 102 || blockIdx.x == 307) && lane == 0 && ntl > 0)
             printf("tpair blk %d wave %d tiles %d: life %llu pro %u | per tile: stage %u w1wait %u bar0 %u phase1 %u bar1 %u halo+issue %u bar2 %u mfma2 %u epilogue2 %u bar3 %u\n",
                    (int)blockIdx.x, wave, ntl, tn - T0, dPro, dStage / ntl, dW1 / ntl, dBar0 / ntl, dPh1 / ntl, dBar1 / ntl, dHalo / ntl, dBar2 / ntl,
@@ -407,31 +398,12 @@ __global__ __launch_bounds__(256, 2) void conv32_tpair_kernel(Conv32P<T> p1, Con
 }
 
 template <typename T>
-static Conv32P<T> tpair_params(const Conv32Args& a, int Hout, int Wout) {
-    Conv32P<T> p;
-    p.in = (const T*)a.in; p.in_nb = a.in_nb > 0 ? a.in_nb : 1;
-    p.wpack = a.w->mbf16; p.wpack2 = (sizeof(T) == 4 || a.w2) ? a.w->mlo : nullptr;
-    p.epi.bias = a.bias;
-    p.epi.up = nullptr; p.epi.up_nb = 1;
-    p.epi.mask = (const T*)a.mask; p.epi.mask_nb = a.mask_nb > 0 ? a.mask_nb : 1;
-    p.epi.add1 = (const T*)a.add1; p.epi.add1_nb = a.add1_nb > 0 ? a.add1_nb : 1;
-    p.epi.add2 = (const T*)a.add2; p.epi.add2_nb = a.add2_nb > 0 ? a.add2_nb : 1;
-    p.epi.out_raw = (T*)a.out_raw; p.epi.out_sum = (T*)a.out_sum;
-    p.epi.mask_bits = a.mask_bits; p.epi.bits_out = a.bits_out; p.epi.bits_nb = a.bits_nb; p.epi.bits_sum = a.bits_sum;
-    p.B = a.B; p.Hin = a.Hin; p.Win = a.Win; p.Hout = Hout; p.Wout = Wout;
-    return p;
-}
-
-// the persistent form's workgroups: the stride-1 kernel's 480 of the 512 two-per-CU slots (conv32.hip kS1Blocks)
-static constexpr int kTpairBlocks = 480;
-
-template <typename T>
 static int launch_tpair_t(const Conv32Args& f, const Conv32Args& g, int form, int max_blocks, hipStream_t s) {
     const int Hm = f.Hin * 2, Wm = f.Win * 2;
-    const Conv32P<T> p1 = tpair_params<T>(f, Hm, Wm), p2 = tpair_params<T>(g, Hm, Wm);
-    const long tiles8 = (long)g.B * ((Wm + 31) / 32) * ((Hm + 7) / 8), tiles4 = (long)g.B * ((Wm + 31) / 32) * ((Hm + 3) / 4);
-    if (form == 0) form = tiles8 > 256 ? 2 : 1;               // (the rule of conv32.hip launch_x3)
-    long blocks = form == 2 ? (tiles8 > kTpairBlocks ? kTpairBlocks : tiles8) : (tiles4 > 1024 ? 1024 : tiles4);
+    const Conv32P<T> p1 = conv32_params<T>(f, Hm, Wm), p2 = conv32_params<T>(g, Hm, Wm);
+    if (form == 0) form = conv32_s1_small_map(g.B, Hm, Wm) ? 1 : 2;      // as the stride-1 launch would choose its kernel
+    // the persistent form's workgroups: the stride-1 kernel's share of the two-per-CU slots (conv32_launch.h kS1PersistentBlocks)
+    long blocks = form == 2 ? conv32_grid(conv32_tiles(g.B, Hm, Wm, X3_TH), kS1PersistentBlocks) : conv32_grid(conv32_tiles(g.B, Hm, Wm, X3S_TH), kS1SmallBlocks);
     if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
     if constexpr (sizeof(T) == 2) {
         if (f.w2) {            // the data gradients' form
@@ -450,10 +422,10 @@ static int launch_tpair_t(const Conv32Args& f, const Conv32Args& g, int form, in
         }
     }
 #endif
-#define KT_(TH_, A_) hipLaunchKernelGGL((conv32_tpair_kernel<T, TH_, A_>), dim3((unsigned)blocks), dim3(256), 0, s, p1, p2)
-    if (form == 2) { if (g.add1) KT_(8, true); else KT_(8, false); }
-    else { if (g.add1) KT_(4, true); else KT_(4, false); }
-#undef KT_
+    with_flag(g.add1 != nullptr, [&](auto ADD) {
+        if (form == 2) hipLaunchKernelGGL((conv32_tpair_kernel<T, 8, decltype(ADD)::value>), dim3((unsigned)blocks), dim3(256), 0, s, p1, p2);
+        else hipLaunchKernelGGL((conv32_tpair_kernel<T, 4, decltype(ADD)::value>), dim3((unsigned)blocks), dim3(256), 0, s, p1, p2);
+    });
     PTTA_CHECK_LAUNCH();
     return 0;
 }
@@ -465,21 +437,8 @@ static int launch_tpair_t(const Conv32Args& f, const Conv32Args& g, int form, in
 // max_blocks > 0 caps the grid (a block then walks several tiles).
 bool ptta_conv32_tpair_applies(const Conv32Args& first, const Conv32Args& second) {
     const Conv32Args &f = first, &g = second;
-    if (!f.w || !g.w || !f.in) return false;
-    if (f.mode != CONV_T2 || g.mode != CONV_S1 || f.bf16 != g.bf16 || f.naive || g.naive || (!f.bf16 && (!f.x3 || !g.x3))) return false;
-    if (f.w2 != g.w2) return false;
-    if (f.bits_out && (f.bits_sum || f.bf16)) return false;
-    if (g.bits_out && g.bf16) return false;
-    if (f.w2) {
-        // the data gradients (narrow maps, hi + lo weights, no ReLU): first = mask . conv, sum = that + one addend; second reads the SUM, masked
-        if (!f.bf16 || f.relu_in || g.relu_in || f.up || g.up || f.bits_out || g.bits_out) return false;
-        if (!f.mask || !f.mask_bits || !f.add1 || f.add2 || !f.out_sum) return false;
-        if (!g.mask || !g.mask_bits || g.add1 || g.add2 || g.out_sum || !g.out_raw) return false;
-    } else {
-        // the forward: ReLU on both inputs, first without epilogue operands, second with up to two addends
-        if (!f.relu_in || f.up || f.mask || f.add1 || f.add2 || f.out_sum || f.mask_bits) return false;
-        if (!g.relu_in || g.up || g.mask || g.mask_bits || (g.add2 && !g.add1) || (g.add1 && !g.out_sum) || (!g.out_raw && !g.out_sum)) return false;
-    }
+    if (f.mode != CONV_T2 || !conv32_pair_common(f, g)) return false;
+    if (!f.w2 && (g.up || (g.add1 && !g.out_sum))) return false;       // the forward's second half: no bilinear skip; addends go to the sum output
     const int Hm = f.Hin * 2, Wm = f.Win * 2;
     return f.Hin >= 1 && f.Win >= 1 && g.Hin == Hm && g.Win == Wm && g.B == f.B && f.B >= 1;
 }
@@ -492,8 +451,7 @@ bool ptta_conv32_tpair_applies(const Conv32Args& first, const Conv32Args& second
 bool ptta_conv32_tpair_pays(const Conv32Args& first, const Conv32Args& second) {
     if (!first.w2) return true;
     const int Hm = first.Hin * 2, Wm = first.Win * 2;
-    const long tiles8 = (long)second.B * ((Wm + 31) / 32) * ((Hm + 7) / 8);
-    return tiles8 <= kTpairBlocks;
+    return conv32_tiles(second.B, Hm, Wm, X3_TH) <= kS1PersistentBlocks;
 }
 int ptta_launch_conv32_tpair(const Conv32Args& first, const Conv32Args& second, int form, int max_blocks, hipStream_t s) {
     if (form < 0 || form > 2 || !ptta_conv32_tpair_applies(first, second)) return 1;

@@ -1,7 +1,7 @@
 // Matrix-core path of the generic NHWC convolution (NLSPN backbone): stride-1 3x3 (and 1x1) convolutions with any
 // channel counts that are multiples of 8, one or two channel-concatenated sources, fp32 storage, bf16x3 arithmetic
 // (x = xh + xl, w = wh + wl; xl*wh + xh*wl + xh*wh on v_mfma_f32_32x32x16_bf16, fp32 accumulate) -- the same
-// arithmetic as the MSG_CHN hot path (conv32.hip), generalised over input-channel chunks and output-channel tiles.
+// arithmetic as the MSG_CHN hot path (conv32.hip and its kernel files conv32_*.hip), generalised over input-channel chunks and output-channel tiles.
 //
 // Block = 256 threads = 4 waves, output tile 8 rows x 32 pixels x 32 output channels (one MFMA column fragment).
 // K loop over 16-channel sub-chunks of the source(s): the (8+2)x(32+2) halo of the sub-chunk is split into bf16 hi/lo
@@ -81,7 +81,6 @@ __global__ void gfrag_pack_kernel(const float* __restrict__ canon, long wld, lon
 // gnet.h Op::rH/rW): three taps, no horizontal halo -- a third of the MFMAs of the zero-padded 3x3 form it replaces.
 // TIMING: s_memtime stamps around the phases of one block's K loop, printed by two blocks of the launch (diagnostic builds of the
 // launcher are compiled with -DPTTA_DIAG_STAMPS; the shipped instantiation has no stamps)
-#define STAMP(v) do { if constexpr (TIMING) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); v = t_; } } while (0)
 // SIX: three operand planes (GX3Args::six_B): 112 B of LDS per pixel, three weight planes, two blocks per CU; blocks of images
 // >= six_B (the proxy frames) skip the three extra products
 // ACTF: the affine epilogue's act_first form, relu(relu(fmaf(..)) + res) (GX3Args::aff_act_first): the inner ReLU in the register layout,
@@ -92,7 +91,7 @@ template <int KS, bool VERT, bool TIMING = false, bool SIX = false, bool ACTF = 
 __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p) {
     unsigned long long T0 = 0, ta = 0, tb = 0, tc = 0, td = 0, te = 0, tf = 0, tg = 0;
     unsigned long long dA = 0, dW = 0, dS = 0, dL = 0, dB = 0, dM = 0;
-    STAMP(T0);
+    PTTA_STAMP(T0);
     constexpr int PAD = KS / 2, PADX = VERT ? 0 : PAD, KKX = VERT ? 1 : KS, PH = GX_TH + 2 * PAD, PW = 32 + 2 * PADX, KK = KS * KKX;
     constexpr int NPIX = PH * PW;
     constexpr int NIT = (NPIX * 2 + 255) / 256;          // (pixel, 8-channel group) items per thread
@@ -178,13 +177,13 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
     const float bias = (cok && p.bias) ? p.bias[co] : 0.f;
     // the eval affine's two values of this lane's channel, fetched with the bias (GX3Args::scale)
     const float asc = (cok && p.scale) ? p.scale[co] : 1.f, ash = (cok && p.scale) ? p.shift[co] : 0.f;
-    unsigned long long Tpro = 0; STAMP(Tpro);
+    unsigned long long Tpro = 0; PTTA_STAMP(Tpro);
     for (int q = 0; q < nq; ++q) {
-        STAMP(ta);
+        PTTA_STAMP(ta);
         if (q) lds_barrier();                            // previous sub-chunk's MFMAs are done with the LDS tile
-        STAMP(tb);
+        PTTA_STAMP(tb);
         if constexpr (TIMING) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        STAMP(tc);
+        PTTA_STAMP(tc);
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int idx = tid + 256 * it;
@@ -213,11 +212,11 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
             const int idx = tid + 256 * j;
             if (idx < NWF) wlds[idx] = wr[j];
         }
-        STAMP(td);
+        PTTA_STAMP(td);
         if (q + 1 < nq) issue_loads(q + 1);
-        STAMP(te);
+        PTTA_STAMP(te);
         lds_barrier();                                   // LDS-only: the loads just issued stay in flight during the MFMAs
-        STAMP(tf);
+        PTTA_STAMP(tf);
         __builtin_amdgcn_s_setprio(1);                    // MFMA phase outranks the other blocks' staging code at issue
 #pragma unroll
         for (int tap = 0; tap < KK; ++tap) {
@@ -257,10 +256,10 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[1], bh, acc[1], 0, 0, 0);
         }
         __builtin_amdgcn_s_setprio(0);
-        STAMP(tg);
+        PTTA_STAMP(tg);
         dA += tb - ta; dW += tc - tb; dS += td - tc; dL += te - td; dB += tf - te; dM += tg - tf;
     }
-    unsigned long long Tloop = 0; STAMP(Tloop);
+    unsigned long long Tloop = 0; PTTA_STAMP(Tloop);
     float s1 = 0.f, s2 = 0.f;
     auto activate = [&](float v) {
         if (p.act == GACT_RELU) v = v > 0.f ? v : 0.f;
@@ -289,7 +288,7 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
     unsigned long long E1 = 0, E2 = 0, E3 = 0;
     if (wide) {
         lds_barrier();                                    // every wave is done with the tile buffers
-        STAMP(E1);
+        PTTA_STAMP(E1);
         float* const tw = (float*)lds + wave * 2048;
         float bias_w = bias;
         if (sig) {                                        // uniform
@@ -317,7 +316,7 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // wave-local: a wave's LDS operations execute in order
-        STAMP(E2);
+        PTTA_STAMP(E2);
         const int c4 = (lane & 7) * 4, pl = lane >> 3;
         const int cbase = nf * 32 - p.nf0 * 32 + c4;
         if (cbase < p.Cy) {
@@ -369,7 +368,7 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
         }
     }
     }
-    STAMP(E3);
+    PTTA_STAMP(E3);
     if (p.stat_part) {
         // fused BatchNorm statistics of this tile: lane halves, then the four waves through LDS (fixed order)
         s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
@@ -386,7 +385,7 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
         }
     }
     if constexpr (TIMING) {
-        unsigned long long Tend = 0; STAMP(Tend);
+        unsigned long long Tend = 0; PTTA_STAMP(Tend);
         if ((blockIdx.x == gridDim.x / 2 || blockIdx.x == gridDim.x / 3) && lane == 0)
             printf("blk %u/%u wave %d nq %d: life %llu pro %llu loop %llu epi %llu (barrier %llu transpose-write %llu read+store %llu stats %llu) | barA %llu vmwait %llu split %llu issue %llu barB %llu mfma %llu\n", blockIdx.x, gridDim.x, wave, nq,
                    Tend - T0, Tpro - T0, Tloop - Tpro, Tend - Tloop, E1 - Tloop, E2 - E1, E3 - E2, Tend - E3, dA, dW, dS, dL, dB, dM);

@@ -181,7 +181,7 @@ int conv32w(ptta_ctx* c, hipStream_t s, const ConvW* w, const float* bias, const
 }
 
 // Conv2d(cin <= 3, 32) - ReLU - Conv2d(32, 32) of an encoder stage's `init` block: ONE launch where the fused form applies
-// (conv32.hip conv32_s1_first_kernel; PTTA_FUSE_FIRST=0 or any other mode: the two launches).  `f`: the first convolution (out_raw = where
+// (conv32_first.hip conv32_s1_first_kernel; PTTA_FUSE_FIRST=0 or any other mode: the two launches).  `f`: the first convolution (out_raw = where
 // its pre-activation map goes), a_nb: how many leading frames of that map are still needed (the backward's ReLU mask), 0: none.
 static int conv32_first(ptta_ctx* c, hipStream_t s, const std::string& layer, ConvInArgs& f, int a_nb, int B, int H, int W, const E& e) {
     auto it = c->l32.find(layer);
@@ -210,7 +210,7 @@ static int conv32_first(ptta_ctx* c, hipStream_t s, const std::string& layer, Co
 }
 
 // Backward of a prediction head in one launch: d v = conv^T_{1->32}(g) * (v > 0) formed per halo tile and consumed by the data gradient of
-// prdct.1 (mask epilogue) -- the d v map is never written (conv32.hip conv32_s1_first_kernel<1, false, true, false, true>).  Large maps only.
+// prdct.1 (mask epilogue) -- the d v map is never written (conv32_first.hip conv32_s1_first_kernel<1, false, true, false, true>).  Large maps only.
 int conv32_first_bwd(ptta_ctx* c, hipStream_t s, const std::string& layer, ConvInArgs& f, int B, int H, int W, const E& e) {
     auto it = c->l32.find(layer);
     if (it == c->l32.end()) return c->fail("unknown 32->32 layer " + layer, -2);

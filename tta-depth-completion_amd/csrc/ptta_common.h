@@ -479,7 +479,11 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
-// ---- the tuned 32 -> 32 convolution kernels' shared pieces (conv32.hip, conv_pair.hip) ----------------------------------------
+// In-kernel phase stamp of the diagnostic instantiations (make DIAG=1 only): v = s_memtime, in a kernel template with a `TIMING`
+// parameter; nothing at all where TIMING is false
+#define PTTA_STAMP(v) do { if constexpr (TIMING) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); v = t_; } } while (0)
+
+// ---- the tuned 32 -> 32 convolution kernels' shared pieces (conv32_device.h and the conv32_*.hip / conv_pair.hip / conv_tpair.hip kernels) ----
 // kernel parameters of one 32 -> 32 launch
 template <typename T>
 struct Conv32P {

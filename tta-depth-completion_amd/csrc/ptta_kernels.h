@@ -21,7 +21,7 @@ inline PttaCreateEnv ptta_create_env() {
     return e;
 }
 
-// ---- conv32.hip ------------------------------------------------------------------------------
+// ---- conv32.hip (the launcher) and its kernel files conv32_ref / _s1 / _strided / _first / _loop.hip; internal: conv32_launch.h ----
 struct ConvW {           // one packed 3x3 32->32 filter, three formats (device memory)
     float* mf32;         // fp32 MFMA fragments  [9][4][64][4]
     bf16_t* mbf16;       // bf16 MFMA fragments  [9][2][64][8] (= hi half of the bf16x3 split)
@@ -56,7 +56,7 @@ int ptta_launch_conv32_pair(const Conv32Args& first, const Conv32Args& second, h
 bool ptta_conv32_tpair_applies(const Conv32Args& first, const Conv32Args& second);
 bool ptta_conv32_tpair_pays(const Conv32Args& first, const Conv32Args& second);      // form 0: the sites where the one launch measured faster
 int ptta_launch_conv32_tpair(const Conv32Args& first, const Conv32Args& second, int form, int max_blocks, hipStream_t s);
-// layer-loop trial (conv32.hip conv32_s1_small_loop_kernel; tools/bench_chain.py): `reps` dependent plain stride-1 layers in one launch
+// layer-loop trial (conv32_loop.hip conv32_s1_small_loop_kernel; tools/bench_chain.py): `reps` dependent plain stride-1 layers in one launch
 int ptta_launch_conv32_loop(const Conv32Args& a, void* buf_a, void* buf_b, int reps, unsigned* ctr, unsigned* base_io, int* err, int variant, hipStream_t s);
 
 // ---- conv_small.hip ---------------------------------------------------------------------------
@@ -85,7 +85,7 @@ int ptta_conv_in_form(const ConvInArgs& a);
 void ptta_pack_conv_in(const float* src, int cin_total, int cin_first, int cin, int transpose_flip,
                        float* wfrag, float* wcanon, hipStream_t s);
 int ptta_launch_conv_in(const ConvInArgs& a, hipStream_t s);
-// the first two layers of an encoder stage in one launch (conv32.hip conv32_s1_first_kernel); returns 1 when not applicable
+// the first two layers of an encoder stage in one launch (conv32_first.hip conv32_s1_first_kernel); returns 1 when not applicable
 int ptta_launch_conv32_first(const Conv32Args& a, const ConvInArgs& f, void* a_out, int a_nb, hipStream_t s);
 
 struct ConvOut1Args {    // 32-channel NHWC -> planar fp32, 1 channel
@@ -388,7 +388,7 @@ struct GX3Args {
     // of a [real | proxy] launch (the reference's no_grad pass) and every data-gradient launch (x1_from_B = 0)
     int x1_from_B = 1 << 30;
     // ... with the WEIGHT operand kept as hi + lo (two MFMAs: a_hi w_lo, a_hi w_hi): the data gradients.  A bf16-rounded weight is a systematic
-    // error of the gradient's direction (conv32.hip mma_step W2), a rounded gradient value is noise
+    // error of the gradient's direction (conv32_device.h mma_step W2), a rounded gradient value is noise
     int x1_w2 = 0;
     // optional per-channel affine behind the convolution (a BatchNorm2d evaluated from constant statistics: the {scale, shift} rows of its
     // st_eval table, indexed by the channel inside the output view) and the BasicBlock residual (pixel stride ld_res, same channels as y):

@@ -850,7 +850,7 @@ int ptta_op_conv32_chain(const float* in, const float* weight, const float* bias
         if ((epi_flags & 4) && aux) { a.add1 = aux; a.add1_nb = b; }
         return ptta_launch_conv32(a, st);
     };
-    if (epi_flags & 16) {                  // the layer loop: `reps` dependent layers per LAUNCH, a device-wide barrier between layers (conv32.hip)
+    if (epi_flags & 16) {                  // the layer loop: `reps` dependent layers per LAUNCH, a device-wide barrier between layers (conv32_loop.hip)
         hipEvent_t d0 = nullptr, d1 = nullptr;
         unsigned* ctr = nullptr; int* err = nullptr;
         int rcd = (hipEventCreate(&d0) != hipSuccess || hipEventCreate(&d1) != hipSuccess) ? -5 : (hipMalloc((void**)&ctr, 256) != hipSuccess ? -12 : 0);
