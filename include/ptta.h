@@ -405,6 +405,24 @@ int ptta_ingest_raw(const uint8_t* image_u8, const uint16_t* sparse_u16, const u
                     float* validity_out, float* gt_out, float* gt_validity_out, int n, int src_height, int src_width, int height, int width,
                     const int32_t* start_y, const int32_t* start_x, float multiplier, ptta_stream s);
 
+/* Eval-time hole filling on device (src/nlspn_model_adapt.py:124-127; the definition is proxytta/inpaint.py, the scipy restatement of
+ * skimage.restoration.inpaint_biharmonic): per sample of the N x 1 x height x width fp32 map `depth`, the exact zeros are the unknowns of
+ * the biharmonic system the host code builds (radius-2 box clipped to the image, Laplacian with replicated box edges, known pixels on the
+ * right-hand side in fp64); it is solved by conjugate gradients in fp64 from x = 0 until |r| <= rtol |b|, and each hole becomes
+ * (float) clip(x, lo, hi) with lo / hi the fp32 min / max of that sample's known pixels.  Every other pixel keeps its bits.  In place.
+ * status (device, n int32) per sample:
+ *   >= 0  filled; the number of iterations used (0: the sample has no holes, or its right-hand side is zero and x = 0)
+ *   -1    not converged within max_iter, or a breakdown (p.Ap <= 0, a non-finite scalar): the sample is left bit for bit as it was
+ *   -2    every pixel is a hole: untouched            -3    more than max_unknowns holes: untouched
+ * scratch: ptta_inpaint_scratch_bytes(n, height, width, max_unknowns) bytes of device memory, 16-byte aligned, contents irrelevant
+ * (-22 from the size function for arguments the call would refuse, and for a size past int64).  -22 before any launch: a NULL pointer, n < 1, a size below 5,
+ * height x width >= 2^31, max_unknowns < 1, max_iter < 1, an rtol that is not a positive finite number, a scratch that is too small or
+ * not 16-byte aligned.  Two launches of one workgroup per sample, no atomics, no wait of one workgroup on another, every loop bounded by
+ * max_iter: results are bit-identical from run to run.  Handle-free, enqueues only. */
+int64_t ptta_inpaint_scratch_bytes(int n, int height, int width, int max_unknowns);
+int ptta_inpaint_biharmonic(float* depth, int n, int height, int width, int max_unknowns, int max_iter, double rtol, void* scratch,
+                            int64_t scratch_bytes, int32_t* status, ptta_stream s);
+
 /* The other augmentations the adapt scripts enable (bash/adapt/adapt_msgchn_vkitti.sh:34-41; applied in every step,
  * src/tta_main.py:595-605).  The reference implements them with torchvision.transforms.functional 0.10.1 (third party, absent
  * from the reference tree: parity unpinned); each call restates torchvision's tensor algorithm.  All handle-free, enqueue only,

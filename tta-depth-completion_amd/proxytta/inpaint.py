@@ -13,7 +13,12 @@ skimage.restoration.inpaint_biharmonic(image, mask) for a single-channel N-d ima
   * the sparse system is solved directly and the result clipped to [min, max] of the known pixels.
 The reference passes each sample as a (1, H, W) array, i.e. a 3-D image one voxel thick: the clipped stencil has extent 1 along
 that axis and reduces to the 2-D biharmonic operator.
+
+`inpainting_device` at the end of this file is the same filling on the device (csrc/inpaint.hip); the functions above are its definition
+and its fallback.
 """
+import ctypes
+
 import numpy as np
 import scipy.ndimage as ndi
 from scipy import sparse
@@ -81,3 +86,45 @@ def inpainting(depth_map):
         depth = depth_map[i, ...]
         depth_map[i] = inpaint_biharmonic(depth, depth == 0)
     return depth_map
+
+
+_device_buffers = {}
+
+
+def inpainting_device(depth_tensor, max_unknowns=65536, max_iter=2000, rtol=1e-12):
+    """`inpainting` on the device (include/ptta.h ptta_inpaint_biharmonic): depth_tensor is a contiguous N x 1 x H x W fp32 CUDA tensor,
+    filled in place on the current stream and returned.  The same system as above, one per sample, solved by conjugate gradients in fp64
+    (stop at |r| <= rtol |b|, at most max_iter iterations: 2000 covers holes about 50 pixels across) and clipped and rounded as above: the
+    filled values agree with the host's to the last fp32 bit or two.  Only the n status words come back to the host.  A sample the
+    device did not fill (status < 0: not converged or a breakdown, more than max_unknowns holes, every pixel a hole) is left as it was by
+    the kernel and goes through `inpaint_biharmonic` on the host, which raises ValueError for a sample without a known pixel.
+    Returns the tensor; `inpainting_device.last_status` holds the status words of the last call (a list)."""
+    import torch
+    from . import _lib
+    from ._lib import ptr
+    lib = _lib.load()
+    t = depth_tensor
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == 1 and t.is_contiguous()):
+        raise ValueError('inpainting_device takes a contiguous N x 1 x H x W fp32 CUDA tensor')
+    n, _, h, w = t.shape
+    key = (t.device, n, h, w, int(max_unknowns))
+    if key not in _device_buffers:
+        size = lib.ptta_inpaint_scratch_bytes(n, h, w, int(max_unknowns))
+        if size < 0:
+            raise RuntimeError('ptta_inpaint_scratch_bytes failed (%d)' % size)
+        _device_buffers[key] = (torch.empty((size + 7) // 8, device=t.device, dtype=torch.float64), torch.empty(n, device=t.device, dtype=torch.int32))
+    scratch, status = _device_buffers[key]
+    rc = lib.ptta_inpaint_biharmonic(ptr(t), n, h, w, int(max_unknowns), int(max_iter), float(rtol), ptr(scratch), scratch.numel() * 8, ptr(status),
+                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != 0:
+        raise RuntimeError('ptta_inpaint_biharmonic failed (%d)' % rc)
+    codes = status.cpu().tolist()                              # the one read-back; it also orders the host behind the launches
+    inpainting_device.last_status = codes
+    for i, code in enumerate(codes):
+        if code < 0:
+            depth = t[i].cpu().numpy()
+            t[i].copy_(torch.from_numpy(inpaint_biharmonic(depth, depth == 0)))
+    return t
+
+
+inpainting_device.last_status = []

@@ -14,8 +14,9 @@ model (the loaded checkpoint, BatchNorm2d from its running statistics); after ad
 prepared it is the BatchNorm-adaptation baseline (gamma / beta of every BatchNorm2d adapt, 86 tensors, batch statistics in train and eval mode).
 Any frame size from 16 x 16 up: encoder maps of odd size make the decoder maps one row / column larger and they are cropped
 before each concatenation as in nlspnmodel_adapt.py:474-490 (NYUv2's 228 x 304 is such a size).
-The eval path's biharmonic hole filling (src/nlspn_model_adapt.py:124-127, skimage on the CPU) is not applied: exact
-zeros of the clamped output are returned as zeros.
+The eval path's biharmonic hole filling (src/nlspn_model_adapt.py:124-127, skimage on the CPU) is `_fill` below: `fill_holes` True (the
+default) runs it on the host as the reference does, 'device' on the device (include/ptta.h ptta_inpaint_biharmonic), False returns the exact
+zeros of the clamped output as zeros.
 """
 import torch
 
@@ -60,7 +61,7 @@ class NlspnModel_Adapt(_AdapterBase):
         self.legacy = bool(offset)                            # args.legacy = offset (src/nlspn_model_adapt.py:62)
         self.max_depth = max_depth
         self.adapt_mode = 'meta_bn'
-        self.fill_holes = True            # eval forward: biharmonic hole filling like the reference (False: the raw network output)
+        self.fill_holes = True            # eval forward: biharmonic hole filling like the reference, on the host ('device': on the device; False: the raw network output)
         super().__init__(max_depth, max_input_depth, device)
 
     @staticmethod
@@ -133,7 +134,17 @@ class NlspnModel_Adapt(_AdapterBase):
         # Fill in any holes with inpainting (src/nlspn_model_adapt.py:124-127): exact zeros left by the final clamp are filled by
         # biharmonic interpolation on the host, as in the reference (scikit-image there; proxytta/inpaint.py restates it on scipy).
         # One flag comes back first: a map without holes -- the usual case -- never leaves the device.
-        if self.fill_holes and 'head' not in loss_type and bool((out == 0).any()):
+        # fill_holes = 'device': the same system solved on the device (proxytta/inpaint.py inpainting_device, include/ptta.h
+        # ptta_inpaint_biharmonic); the map stays there and only one status word per sample comes back.  A sample the device could not fill
+        # goes through the host code, as under True.
+        if self.fill_holes not in (False, True, 'device'):
+            raise ValueError("fill_holes is False, True (the host path) or 'device', not %r" % (self.fill_holes,))
+        if not self.fill_holes or 'head' in loss_type:
+            return out
+        if self.fill_holes == 'device':
+            from .inpaint import inpainting_device
+            return inpainting_device(out.detach().clone(memory_format=torch.contiguous_format))
+        if bool((out == 0).any()):
             from .inpaint import inpainting
             out = torch.from_numpy(inpainting(out.detach().cpu().numpy())).to(out.device)
         return out
