@@ -423,6 +423,68 @@ int64_t ptta_inpaint_scratch_bytes(int n, int height, int width, int max_unknown
 int ptta_inpaint_biharmonic(float* depth, int n, int height, int width, int max_unknowns, int max_iter, double rtol, void* scratch,
                             int64_t scratch_bytes, int32_t* status, ptta_stream s);
 
+/* The summary panels of the plugin's log_summary (src/external_model_adapt.py:662-909) composed on device: ONE launch writes the complete
+ * grid the reference hands to summary_writer.add_image -- torch.cat of the rows, torchvision's make_grid(nrow = n_image_per_summary,
+ * padding 2, pad value 0) and log_utils.colorize (:53-80) included -- so that one copy of the finished grid leaves the card instead of up to
+ * five fp32 maps.  Per shown sample i < n_show a panel of R rows, each `height` high and 2 `width` wide, stacked along the height, in this order:
+ *   image k < n_images   left: image[k][i] after the display transform                 right: zeros
+ *   PTTA_SUMMARY_ROW_OUTPUT  left: viridis(output_depth / max_predict_depth)           right: zeros
+ *   PTTA_SUMMARY_ROW_SPARSE  left: viridis(sparse_depth / max_predict_depth)           right: inferno(e_s / 0.05f)
+ *   PTTA_SUMMARY_ROW_GT      left: viridis(ground_truth / max_predict_depth)           right: inferno(e_g / 0.05f)
+ *   e_s = validity_map > 0 ? |out - sparse| / (sparse + 1e-8f) : validity_map                       (:820-825)
+ *   e_g = ground_truth > 0 ? (|out - gt| + 1e-8f) / (gt + 1e-8f) : 0                                (:846-863)
+ * Display transform (:738-766): x / 255.0f when *image_div255[k] != 0 (NULL: never), then (x - rev_mean[c]) / rev_std[c] when `normalize`.
+ * Colormap of x, with t = x * 256.0f in fp32: NaN -> (0, 0, 0); t < 0 -> entry 0; t >= 256 -> entry 255; else entry trunc(t); the value
+ * written is the fp64 table entry rounded to fp32.  `viridis` / `inferno` are 256 x 3 fp64 device tables (matplotlib's `.colors`); the
+ * library embeds none.  Every value is a table entry or a chain of single correctly rounded fp32 operations (IEEE division, no fma):
+ * the grid equals the reference's bit for bit.
+ * Grid: n_show == 1: the panel itself, 3 x (R height) x (2 width).  n_show > 1: 3 x (R height + 4) x (n_show (2 width + 2) + 2), panel i at
+ * row 2, column i (2 width + 2) + 2, zeros elsewhere.  ptta_summary_grid_shape (pure host) returns the two sizes.
+ * out: PTTA_SUMMARY_OUT_F32_CHW: fp32 3 x GH x GW.  PTTA_SUMMARY_OUT_U8_HWC: uint8 GH x GW x 3 holding (uint8) clamp(v * 255.0f, 0, 255)
+ * by truncation, NaN -> 0: the conversion torch.utils.tensorboard applies to a float image.  Every output element is written exactly once
+ * (padding and zero halves included): the buffer needs no clearing.  16-byte stores where the output base is 16-byte aligned and GH GW is
+ * a multiple of 4 (uint8: 12 bytes per lane on a 4-byte-aligned base); one pixel per lane otherwise, same results.
+ * Inputs are fp32, device, image N x 3 x height x width and the maps N x 1 x height x width with N >= n_show; only the first n_show samples are read.
+ * -22 before any launch: a NULL args / output, no row at all, n_images outside 0..PTTA_SUMMARY_MAX_IMAGES, a NULL image, a row bit without
+ * its inputs (OUTPUT: output_depth; SPARSE: OUTPUT + sparse_depth + validity_map; GT: OUTPUT + ground_truth), unknown row bits or out_dtype,
+ * n_show < 1, a size < 1, GH GW 3 >= 2^31, a max_predict_depth that is not a positive finite number, a NULL table while a coloured
+ * row is requested.  Handle-free, enqueues only, no atomics.
+ *
+ * ptta_summary_image_flag: the `torch.max(img) > 10.0` test of the display transform, on device: flag[0] = 1 when some element of
+ * image[0 .. count) is > 10 and none is NaN (torch.max propagates NaN and NaN > 10 is false), else 0.  count covers the WHOLE tensor, not
+ * only the shown samples.  `flag` is PTTA_SUMMARY_FLAG_WORDS int32 of device memory (word 0 the flag, the rest per-block partial results;
+ * contents irrelevant on entry).  Two launches (per-block partials, then their union): no atomics, bit-identical from run to run, no host
+ * synchronisation; pass `flag` as image_div255[k] of a compose call enqueued behind it on the same stream.  -22: a NULL or misaligned
+ * pointer, count < 1. */
+#define PTTA_SUMMARY_MAX_IMAGES 8
+#define PTTA_SUMMARY_ROW_OUTPUT 1
+#define PTTA_SUMMARY_ROW_SPARSE 2
+#define PTTA_SUMMARY_ROW_GT 4
+#define PTTA_SUMMARY_OUT_F32_CHW 0
+#define PTTA_SUMMARY_OUT_U8_HWC 1
+#define PTTA_SUMMARY_FLAG_WORDS 257
+typedef struct ptta_summary_args {
+    int n_show, height, width;
+    int n_images;                        /* image rows, in list order */
+    int rows;                            /* PTTA_SUMMARY_ROW_* bits: the depth rows behind the image rows */
+    int normalize;                       /* apply (x - rev_mean[c]) / rev_std[c] to the image rows */
+    int out_dtype;                       /* PTTA_SUMMARY_OUT_* */
+    float max_predict_depth;
+    float rev_mean[3], rev_std[3];       /* float32(-m_c / s_c), float32(1 / s_c) */
+    const float* image[PTTA_SUMMARY_MAX_IMAGES];
+    const int32_t* image_div255[PTTA_SUMMARY_MAX_IMAGES];
+    const float* output_depth;
+    const float* sparse_depth;
+    const float* validity_map;
+    const float* ground_truth;
+    const double* viridis;
+    const double* inferno;
+    void* out;
+} ptta_summary_args;
+int ptta_summary_grid_shape(int n_show, int height, int width, int n_rows, int64_t* grid_height_host, int64_t* grid_width_host);
+int ptta_summary_image_flag(const float* image, int64_t count, int32_t* flag, ptta_stream s);
+int ptta_summary_compose(const ptta_summary_args* a, ptta_stream s);
+
 /* The other augmentations the adapt scripts enable (bash/adapt/adapt_msgchn_vkitti.sh:34-41; applied in every step,
  * src/tta_main.py:595-605).  The reference implements them with torchvision.transforms.functional 0.10.1 (third party, absent
  * from the reference tree: parity unpinned); each call restates torchvision's tensor algorithm.  All handle-free, enqueue only,

@@ -82,6 +82,18 @@ class LossArgs(ctypes.Structure):              # include/ptta.h ptta_loss_args
                 [(n, c_void_p) for n in ('depth', 'image', 'sparse', 'validity', 'emb', 'ref', 'loss_info', 'rowstats', 'gdepth', 'gref', 'coef')])
 
 
+class SummaryArgs(ctypes.Structure):           # include/ptta.h ptta_summary_args
+    _fields_ = ([(n, c_int) for n in ('n_show', 'height', 'width', 'n_images', 'rows', 'normalize', 'out_dtype')] + [('max_predict_depth', c_float)] +
+                [('rev_mean', c_float * 3), ('rev_std', c_float * 3), ('image', c_void_p * 8), ('image_div255', c_void_p * 8)] +
+                [(n, c_void_p) for n in ('output_depth', 'sparse_depth', 'validity_map', 'ground_truth', 'viridis', 'inferno', 'out')])
+
+
+# ptta_summary_args `rows` / `out_dtype`, the size of ptta_summary_image_flag's buffer
+PTTA_SUMMARY_MAX_IMAGES = 8
+PTTA_SUMMARY_ROW_OUTPUT, PTTA_SUMMARY_ROW_SPARSE, PTTA_SUMMARY_ROW_GT = 1, 2, 4
+PTTA_SUMMARY_OUT_F32_CHW, PTTA_SUMMARY_OUT_U8_HWC = 0, 1
+PTTA_SUMMARY_FLAG_WORDS = 257
+
 # ptta_op_loss `fwd` / `bwd`, ptta_op_conv_in's *form_host
 LOSS_FWD = {'merged': 0, 'nocos': 1, 'split': 2, 'split_narrow': 3}
 LOSS_BWD = {'none': 0, 'unfused': 1, 'fused': 2, 'counted': 3}
@@ -136,6 +148,9 @@ SIGNATURES = [
     ('ptta_ingest_raw', c_int, [_P] * 8 + [c_int] * 5 + [_P, _P, c_float, _P]),
     ('ptta_inpaint_scratch_bytes', c_int64, [c_int, c_int, c_int, c_int]),
     ('ptta_inpaint_biharmonic', c_int, [_P, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, _P, c_int64, _P, _P]),
+    ('ptta_summary_grid_shape', c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    ('ptta_summary_image_flag', c_int, [_P, c_int64, _P, _P]),
+    ('ptta_summary_compose', c_int, [POINTER(SummaryArgs), _P]),
     ('ptta_rotate', c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
     ('ptta_resize_crop', c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     ('ptta_photometric', c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -227,5 +242,5 @@ def ptr(t):
     return c_void_p(t.data_ptr())
 
 
-__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs',
+__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs', 'SummaryArgs',
            'LOSS_FWD', 'LOSS_BWD', 'CONV_IN_FORMS', 'SIGNATURES', 'LIB_PATH', 'byref']

@@ -757,6 +757,58 @@ class ExternalModel_Adapt(object):
     def convert_syncbn(self, apex=False):
         self.model.convert_syncbn(apex)
 
+    def log_summary(self, summary_writer, tag, step, image=None, output_image=None, sparse_depth=None, output_depth=None,
+                    validity_map=None, ground_truth=None, normalized_image_range=None, scalars={}, n_image_per_summary=4,
+                    image_dtype='float32'):
+        """src/external_model_adapt.py:662-909, keyword for keyword, with the panels composed on the device (proxytta.summary, csrc/summary.hip).
+        summary_writer is anything with add_image, add_histogram and add_scalar.  image: an N x 3 x H x W tensor or a list of them; the maps
+        N x 1 x H x W; host tensors are uploaded (the driver moves them to the CPU in front of the call, src/tta_main.py:637-640).  The
+        calls, tags, order and global_step are the reference's: add_histogram per depth map with the tensor as given, add_scalar per
+        entry of `scalars` (device scalars are fetched with ONE stacked copy), add_image with the image grid (tag + '_image') and with
+        the depth grid (tag + '_image_output_sparse-error_groundtruth-error' and its shorter forms).  Each grid arrives as a CPU tensor
+        after one device -> host copy: bit for bit the reference's 3 x GH x GW fp32 grid, or with image_dtype='uint8' the GH x GW x 3
+        uint8 image the writer would make of it, passed with dataformats='HWC' (a quarter of the bytes, the same PNG).
+        normalized_image_range=None means "no display transform"; the reference raises TypeError on None[0] there.  output_image is
+        not built (no driver passes it and the reference's branch swaps mean and std): anything but None raises NotImplementedError."""
+        from . import summary
+        if output_image is not None:
+            raise NotImplementedError('log_summary(output_image=...) is not built: no driver passes it and the reference normalises it with '
+                                      'mean and std swapped (src/external_model_adapt.py:780-783)')
+        if image_dtype not in ('float32', 'uint8'):
+            raise ValueError("image_dtype is 'float32' or 'uint8'")
+        device = self.device if torch.device(self.device).type == 'cuda' else torch.device('cuda')
+
+        def resident(t):
+            return None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()
+        with torch.no_grad():
+            images = [] if image is None else [resident(t) for t in (image if isinstance(image, list) else [image])]
+            out_d, sparse_d, valid_d, gt_d = (resident(t) for t in (output_depth, sparse_depth, validity_map, ground_truth))
+            depth_text = tag + ('_image' if images else '')
+            if output_depth is not None:
+                depth_text += '_output'
+                summary_writer.add_histogram(tag + '_output_depth_distro', output_depth, global_step=step)
+                if sparse_depth is not None and validity_map is not None:
+                    depth_text += '_sparse-error'
+                    summary_writer.add_histogram(tag + '_sparse_depth_distro', sparse_depth, global_step=step)
+                if ground_truth is not None:
+                    depth_text += '_groundtruth-error'
+                    summary_writer.add_histogram(tag + '_ground_truth_distro', ground_truth, global_step=step)
+            on_device = [k for k, v in scalars.items() if torch.is_tensor(v) and v.is_cuda]
+            fetched = dict(zip(on_device, torch.stack([scalars[k].detach().reshape(()).double() for k in on_device]).cpu().tolist())) if on_device else {}
+            for name, value in scalars.items():
+                summary_writer.add_scalar(tag + '_' + name, fetched.get(name, value), global_step=step)
+            kw = dict(max_predict_depth=self.max_predict_depth, normalized_image_range=normalized_image_range,
+                      n_image_per_summary=n_image_per_summary, image_dtype=image_dtype)
+            extra = dict(dataformats='HWC') if image_dtype == 'uint8' else {}
+            flags = [summary.image_flag(t) for t in images]
+            if images:
+                grid = summary.compose_grid(image=images, image_flags=flags, **kw)
+                summary_writer.add_image(tag + '_image', summary.to_host(grid), global_step=step, **extra)
+            if images or output_depth is not None:
+                grid = summary.compose_grid(image=images[-1:], image_flags=flags[-1:], output_depth=out_d, sparse_depth=sparse_d,
+                                            validity_map=valid_d, ground_truth=gt_d, **kw)
+                summary_writer.add_image(depth_text, summary.to_host(grid), global_step=step, **extra)
+
     # ---- fused entry points -----------------------------------------------------------------
     def set_image_norm(self, normalized_image_range):
         self.model.set_image_norm(normalized_image_range)
