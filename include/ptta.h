@@ -485,6 +485,61 @@ int ptta_summary_grid_shape(int n_show, int height, int width, int n_rows, int64
 int ptta_summary_image_flag(const float* image, int64_t count, int32_t* flag, ptta_stream s);
 int ptta_summary_compose(const ptta_summary_args* a, ptta_stream s);
 
+/* Scoring a run on device: the tail of the reference's drivers that turns a run into the four numbers of results.txt (adaptation loop
+ * src/tta_main.py:755-809, validate :975-1030), accumulated in device memory with no host synchronisation per frame.  One accumulate call
+ * scores one batch of N x 1 x height x width fp32 maps inside the window [win_y : win_y + win_height, win_x : win_x + win_width] of every
+ * sample (the drivers' bottom-centre crop; the whole frame is win 0, 0, height, width); nothing outside the window is read and the maps
+ * need no cropped copy.
+ *   mask   PTTA_SCORE_RULE_ADAPT (:776-781)       gt > 0 && !(gt < min) && !(gt > max)     a pixel equal to a bound counts
+ *          PTTA_SCORE_RULE_VALIDATE (:1008-1015)  gt > 0 && gt > min && gt < max           a pixel equal to a bound does not
+ *   pixel  d = 1000 gt - 1000 out;  i = 1 / (0.001 gt + 1e-9) - 1 / (0.001 out + 1e-9);  d d and i i: every product, sum and quotient a single
+ *          correctly rounded fp32 operation (no fma), as the reference's fp32 tensors compute them
+ *   sums   count, sum |d|, sum d d, sum |i|, sum i i in fp64, per sample and pooled over the batch
+ *   batch  MAE = sum |d| / count, RMSE = sqrt(sum d d / count) in mm, iMAE, iRMSE likewise in 1/km, in fp64 from the POOLED sums (the
+ *          reference takes one mean over the whole batch and multiplies it by batch_size); count == 0 gives 0 / 0 = NaN as torch.mean of
+ *          an empty tensor does
+ *   state  sum[k] += metric_k n (fp64);  frames += n;  batches += 1;  pixels += count;  empty_batches += (count == 0).  A NaN stays in the
+ *          run; empty_batches says why.
+ * state: ptta_score_state_bytes(max_n) bytes of device memory, 16-byte aligned, handed to ptta_score_reset before its first use (reset
+ * zeroes the run and makes the state's size known to the later calls; a state that was never reset is refused).  Its layout, for callers
+ * that read it on device:
+ *   byte 0    double sum[4]                                        the run's MAE, RMSE, iMAE, iRMSE sums
+ *   byte 32   int64 frames, batches, empty_batches, pixels
+ *   byte 64   double last[5]: count, sum |d|, sum d d, sum |i|, sum i i     pooled, of the latest accumulate call
+ *   byte 128  double sample[max_n][6]: the same five per sample of the latest call, one pad
+ *   then      the per-block partial sums of the latest call
+ * Optional outputs (device, NULL = not wanted): batch_out 4 fp32, the batch's four metrics; sample_out n x 4 fp32, the same from each
+ * sample's own sums (NaN for a sample without a masked pixel); sample_count_out n int32.  The fp32 values are the fp64 ones rounded once.
+ * ptta_score_result writes 8 doubles to device memory: MAE, RMSE, iMAE, iRMSE = sum[k] / (n_sample > 0 ? n_sample : frames) (:806-809; the
+ * reference's / 1000 ... * 1000 cancels), then frames, batches, empty_batches, pixels.
+ * Two launches per accumulate call: partial sums over n x B workgroups, B a fixed function of the window's size (never of timing), then
+ * one workgroup that adds them in a fixed order.  No floating-point atomics, no workgroup waits on another, every loop is bounded by the
+ * arguments: results are bit-identical from run to run.  Both maps are read with 16-byte loads where width, win_x and win_width are
+ * multiples of 4 and both base pointers are 16-byte aligned, one pixel per load otherwise; the two paths add in different orders and may
+ * differ in the last bits of the fp64 sums.  Nothing is written except the state and the optional outputs.
+ * -22 before any launch, with the reason in ptta_last_error(NULL): a NULL args, map or state pointer; n < 1 or n > the state's max_n; a
+ * size < 1; a window that is empty or leaves the sample; min > max or a bound that is not finite; a rule other than the two; a state that is
+ * not 16-byte aligned, was not reset, or is too small (reset: state_bytes below the size for max_n = 1; the size function: max_n < 1 or
+ * above PTTA_SCORE_MAX_N).  Handle-free, enqueue only; one state is used from one stream at a time. */
+#define PTTA_SCORE_MAX_N 4096
+enum { PTTA_SCORE_RULE_ADAPT = 0, PTTA_SCORE_RULE_VALIDATE = 1 };
+typedef struct ptta_score_args {
+    const float* depth;          /* N x 1 x H x W fp32, contiguous */
+    const float* ground_truth;   /* same shape */
+    int n, height, width;
+    int win_y, win_x, win_height, win_width;   /* scoring window inside every sample */
+    float min_evaluate_depth, max_evaluate_depth;
+    int rule;
+    void* state;                 /* ptta_score_state_bytes(max_n) bytes, 16-byte aligned */
+    float* batch_out;            /* optional, 4: this batch's pooled MAE, RMSE (mm), iMAE, iRMSE (1/km) */
+    float* sample_out;           /* optional, n x 4: the same per sample */
+    int32_t* sample_count_out;   /* optional, n: masked pixels per sample */
+} ptta_score_args;
+int64_t ptta_score_state_bytes(int max_n);
+int ptta_score_reset(void* state, int64_t state_bytes, ptta_stream s);
+int ptta_score_accumulate(const ptta_score_args* a, ptta_stream s);
+int ptta_score_result(const void* state, int64_t n_sample, double* out8, ptta_stream s);   /* out8 on the device */
+
 /* The other augmentations the adapt scripts enable (bash/adapt/adapt_msgchn_vkitti.sh:34-41; applied in every step,
  * src/tta_main.py:595-605).  The reference implements them with torchvision.transforms.functional 0.10.1 (third party, absent
  * from the reference tree: parity unpinned); each call restates torchvision's tensor algorithm.  All handle-free, enqueue only,

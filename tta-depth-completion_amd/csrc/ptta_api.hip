@@ -26,6 +26,8 @@ int ptta_version(void) { return PTTA_ABI_VERSION; }
 // why the calling thread's last ptta_create refused a configuration (there is no handle to ask then): ptta_last_error(NULL)
 static thread_local std::string g_create_err;
 static int create_refused(const std::string& why) { g_create_err = why; return -38; }
+// the same slot for a handle-free entry point that refuses its arguments (score.hip)
+extern "C++" int ptta_refuse_args(const char* why) { g_create_err = why; return -22; }
 
 const char* ptta_last_error(ptta_handle h) {
     if (!h) return g_create_err.empty() ? "null handle" : g_create_err.c_str();

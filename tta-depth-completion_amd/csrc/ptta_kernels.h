@@ -249,6 +249,10 @@ int ptta_launch_loss_valid_count(const float* sparse, const float* validity, int
 int ptta_launch_eval_metrics(const float* depth, const float* gt, long n, float min_eval, float max_eval, double* scratch, float* out4,
                              hipStream_t s);
 
+// ---- ptta_api.hip: a handle-free entry point's refusal -----------------------------------------
+// records `why` as what ptta_last_error(NULL) returns on the calling thread, and returns -22
+int ptta_refuse_args(const char* why);
+
 // ---- wgrad_adam.hip ---------------------------------------------------------------------------
 int ptta_wgrad_chunks(long pixels);
 int ptta_launch_wgrad32(const void* x, const void* gy, int bf16, int B, int H, int W, float* part,

@@ -88,6 +88,17 @@ class SummaryArgs(ctypes.Structure):           # include/ptta.h ptta_summary_arg
                 [(n, c_void_p) for n in ('output_depth', 'sparse_depth', 'validity_map', 'ground_truth', 'viridis', 'inferno', 'out')])
 
 
+class ScoreArgs(ctypes.Structure):             # include/ptta.h ptta_score_args
+    _fields_ = ([('depth', c_void_p), ('ground_truth', c_void_p)] +
+                [(n, c_int) for n in ('n', 'height', 'width', 'win_y', 'win_x', 'win_height', 'win_width')] +
+                [('min_evaluate_depth', c_float), ('max_evaluate_depth', c_float), ('rule', c_int)] +
+                [(n, c_void_p) for n in ('state', 'batch_out', 'sample_out', 'sample_count_out')])
+
+
+# ptta_score_args `rule`, the largest max_n a score state is sized for
+PTTA_SCORE_RULE_ADAPT, PTTA_SCORE_RULE_VALIDATE = 0, 1
+PTTA_SCORE_MAX_N = 4096
+
 # ptta_summary_args `rows` / `out_dtype`, the size of ptta_summary_image_flag's buffer
 PTTA_SUMMARY_MAX_IMAGES = 8
 PTTA_SUMMARY_ROW_OUTPUT, PTTA_SUMMARY_ROW_SPARSE, PTTA_SUMMARY_ROW_GT = 1, 2, 4
@@ -151,6 +162,10 @@ SIGNATURES = [
     ('ptta_summary_grid_shape', c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     ('ptta_summary_image_flag', c_int, [_P, c_int64, _P, _P]),
     ('ptta_summary_compose', c_int, [POINTER(SummaryArgs), _P]),
+    ('ptta_score_state_bytes', c_int64, [c_int]),
+    ('ptta_score_reset', c_int, [_P, c_int64, _P]),
+    ('ptta_score_accumulate', c_int, [POINTER(ScoreArgs), _P]),
+    ('ptta_score_result', c_int, [_P, c_int64, _P, _P]),
     ('ptta_rotate', c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
     ('ptta_resize_crop', c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     ('ptta_photometric', c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -242,5 +257,5 @@ def ptr(t):
     return c_void_p(t.data_ptr())
 
 
-__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs', 'SummaryArgs',
+__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs', 'SummaryArgs', 'ScoreArgs',
            'LOSS_FWD', 'LOSS_BWD', 'CONV_IN_FORMS', 'SIGNATURES', 'LIB_PATH', 'byref']
