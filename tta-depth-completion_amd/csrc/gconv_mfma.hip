@@ -26,17 +26,6 @@
 
 namespace {
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float float2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void gsplit2(float a, float b, unsigned& hi, unsigned& lo) {
-    float2_t v = {a, b};
-    const bf16x2_t h = __builtin_convertvector(v, bf16x2_t);
-    hi = __builtin_bit_cast(unsigned, h);
-    float2_t r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_t));
-}
-
 // three-way split a = h + m + l (8 + 8 + 8 significant bits): h and m are the two-way split's (hi, lo); l2 is what that split drops
 __device__ __forceinline__ void gsplit3(float a, float b, unsigned& hi, unsigned& lo, unsigned& l2) {
     float2_t v = {a, b};
@@ -200,8 +189,8 @@ __global__ __launch_bounds__(256, SIX ? 2 : 3) void gconv_x3_s1_kernel(GX3Args p
                     gsplit3(a1.x, a1.y, hi.z, lo.z, l2.z); gsplit3(a1.z, a1.w, hi.w, lo.w, l2.w);
                     *(uint4*)(dst + 64) = l2;
                 } else {
-                    gsplit2(a0.x, a0.y, hi.x, lo.x); gsplit2(a0.z, a0.w, hi.y, lo.y);
-                    gsplit2(a1.x, a1.y, hi.z, lo.z); gsplit2(a1.z, a1.w, hi.w, lo.w);
+                    split2(a0.x, a0.y, hi.x, lo.x); split2(a0.z, a0.w, hi.y, lo.y);
+                    split2(a1.x, a1.y, hi.z, lo.z); split2(a1.z, a1.w, hi.w, lo.w);
                 }
                 *(uint4*)dst = hi;
                 *(uint4*)(dst + 32) = lo;
@@ -494,8 +483,8 @@ __global__ __launch_bounds__(256) void gconv_x3_direct_kernel(GX3Args p, int Hin
                         gsplit3(a1.x, a1.y, hi.z, lo.z, l2.z); gsplit3(a1.z, a1.w, hi.w, lo.w, l2.w);
                         a2[rr] = __builtin_bit_cast(bf16x8, l2);
                     } else {
-                        gsplit2(a0.x, a0.y, hi.x, lo.x); gsplit2(a0.z, a0.w, hi.y, lo.y);
-                        gsplit2(a1.x, a1.y, hi.z, lo.z); gsplit2(a1.z, a1.w, hi.w, lo.w);
+                        split2(a0.x, a0.y, hi.x, lo.x); split2(a0.z, a0.w, hi.y, lo.y);
+                        split2(a1.x, a1.y, hi.z, lo.z); split2(a1.z, a1.w, hi.w, lo.w);
                     }
                     ah[rr] = __builtin_bit_cast(bf16x8, hi); al[rr] = __builtin_bit_cast(bf16x8, lo);
                 }
@@ -691,10 +680,6 @@ __global__ __launch_bounds__(64) void gwgrad_mfma_kernel(GView x, GView gy, int 
 // renames of it (v[0..7], v[1..8], v[2..9]): 38 loads per step instead of 80.  Nine 32 x 32 accumulators per wave; the next
 // step's loads are issued before the current step's 27 MFMAs.  Partials in the layout of gwgrad_mfma_kernel (same reducer).
 // 352x1216, Conv2d(48,48,3): 876 -> see DESIGN.md (the fp32 form alternated a 40-load phase and a 40-MFMA phase per 8 pixels).
-__device__ __forceinline__ void wsplit8(const float* v, uint4& hi, uint4& lo) {
-    gsplit2(v[0], v[1], hi.x, lo.x); gsplit2(v[2], v[3], hi.y, lo.y);
-    gsplit2(v[4], v[5], hi.z, lo.z); gsplit2(v[6], v[7], hi.w, lo.w);
-}
 // single = 1 (Ci, Co <= 32): one tile pair; the four waves take different items instead and write a partial each.
 // BLKRED (single only): the four waves' partial tiles are summed inside the block in a fixed tree ((w0 + w2) + (w1 + w3)) through LDS and the
 // block writes ONE partial -- four times the waves for the same partial traffic: the launch is a latency chain of ~2 us per item and wave
@@ -776,14 +761,14 @@ __global__ __launch_bounds__(256) void gwgrad_x3_kernel(GView x, GView gy, int n
 #pragma unroll
             for (int j = 0; j < 10; ++j) if (!((r.vm[dy] >> j) & 1u)) r.v[dy][j] = 0.f;
         uint4 gh, gl;
-        wsplit8(r.g, gh, gl);
+        split8(r.g, gh, gl);
         const bf16x8 ah = __builtin_bit_cast(bf16x8, gh), al = __builtin_bit_cast(bf16x8, gl);
 #pragma unroll
         for (int j = 0; j < 8; ++j) bsum += r.g[j];
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
             // the row's ten values are split ONCE: packed hi / lo of the five even-aligned pairs (0,1) .. (8,9) and the four odd-aligned pairs
-            // (1,2) .. (7,8); tap dx = 0 / 2 takes even pairs 0..3 / 1..4, dx = 1 the odd ones.  Same conversions as wsplit8 of the three
+            // (1,2) .. (7,8); tap dx = 0 / 2 takes even pairs 0..3 / 1..4, dx = 1 the odd ones.  Same conversions as split8 of the three
             // shifted windows (hi = RNE(v), lo = RNE(v - hi)): identical fragments, 38 instead of 72 conversions.
             const float* v = r.v[dy];
             unsigned eh[5], el[5], oh[4], ol[4];

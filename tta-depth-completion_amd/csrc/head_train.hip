@@ -3,7 +3,7 @@
 // affine gradients (from the backward partials the TTA path already produces), the EMA of the target head.
 //
 // Weight gradient dW[o][i] = sum_r G[r][o] * X[r][i] is a reduction-GEMM over the R = N*H/4*W/4 embedding rows (26,752 per
-// KITTI frame), on the matrix cores with bf16x3 arithmetic like the forward GEMMs (heads.hip).  MFMA operand layout makes
+// KITTI frame), on the matrix cores with bf16x3 arithmetic like the forward GEMMs (heads_x3.hip, heads_ws.hip).  MFMA operand layout makes
 // this one LDS-light: a lane of v_mfma_f32_32x32x16_bf16 holds 8 consecutive k for ONE m (or n); with k = row and m = output
 // column the lane's 8 values sit in 8 consecutive ROWS of one COLUMN of G, so each wave loads its own A fragments straight
 // from global memory (a half-wave reads 32 consecutive floats of one row: 128-B segments) and only the X fragments, shared by
@@ -14,19 +14,6 @@
 // the bias gradient (column sums of the transformed G, accumulated by the blocks of the first X tile).
 #include "ptta_common.h"
 #include "ptta_kernels.h"
-
-typedef __bf16 tbf16x2 __attribute__((ext_vector_type(2)));
-typedef float tfloat2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void tsplit2(float a, float b, unsigned& hi, unsigned& lo) {
-    tfloat2 v = {a, b};
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, tbf16x2));
-    tfloat2 r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, tbf16x2));
-}
-__device__ __forceinline__ void tsplit8(const float* v, uint4& hi, uint4& lo) {
-    tsplit2(v[0], v[1], hi.x, lo.x); tsplit2(v[2], v[3], hi.y, lo.y);
-    tsplit2(v[4], v[5], hi.z, lo.z); tsplit2(v[6], v[7], hi.w, lo.w);
-}
 
 // NT = number of 32-column X tiles per block (4: I = 512 in 128-column tiles; 1: I = 32)
 template <int NT, int GPRO, int XPRO>
@@ -79,7 +66,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(LinWgradArgs a) {
             g[j] = v; bsum += v;
         }
         uint4 ah, al;
-        tsplit8(g, ah, al);
+        split8(g, ah, al);
         // ---- X fragment of tile (wave % NT), staged once per block through LDS ------------------------
         if (wave < NT) {
             float x[8];
@@ -90,7 +77,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(LinWgradArgs a) {
                 x[j] = v;
             }
             uint4 xh, xl;
-            tsplit8(x, xh, xl);
+            split8(x, xh, xl);
             Bs[stage][wave][0][lane] = xh; Bs[stage][wave][1][lane] = xl;
         }
         if (r0 + 16 < r_end) fetch(r0 + 16);

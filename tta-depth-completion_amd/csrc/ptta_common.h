@@ -427,7 +427,7 @@ __device__ __forceinline__ void epi_tile(const Epi<T>& e, int b, int y, int H, i
 
 // MFMA 32x32 accumulator row of register r for lane half h (cdna_hip_programming.md §3):
 // row = (r&3) + 8*(r>>2) + 4*h, col = lane&31.
-// d loss_cos / d ref, one element: coef (e / |e| - c ref / |ref|) / |ref| with ie = 1 / |e|, ir = 1 / |ref| (loss.hip cos_grad_body; heads.hip PRO 4:
+// d loss_cos / d ref, one element: coef (e / |e| - c ref / |ref|) / |ref| with ie = 1 / |e|, ir = 1 / |ref| (loss.hip cos_grad_body; heads_ws.hip PRO 4:
 // the same expression in both, but the compiler is free to contract it differently in the two kernels -- last-bit differences)
 __device__ __forceinline__ float cos_grad_elem(float coef, float e, float r, float ie, float ir, float proj) {
     return coef * (e * ie - proj * r * ir) * ir;
@@ -512,6 +512,10 @@ __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned&
     hi = __builtin_bit_cast(unsigned, h);
     float2_t r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_t));
+}
+__device__ __forceinline__ void split8(const float* v, uint4& hi, uint4& lo) {
+    split2(v[0], v[1], hi.x, lo.x); split2(v[2], v[3], hi.y, lo.y);
+    split2(v[4], v[5], hi.z, lo.z); split2(v[6], v[7], hi.w, lo.w);
 }
 // ReLU of two packed bf16: sign-magnitude values ordered as int16 -> one v_pk_max_i16 against zero (-0.0 -> +0.0)
 __device__ __forceinline__ unsigned relu_pk(unsigned v) {

@@ -131,7 +131,7 @@ struct PttaStatSync {
 int ptta_stat_sync(const PttaStatSync* sy, float* part, int nblocks, int C, int npass, hipStream_t s);      // gbn.hip
 int ptta_grad_mean_sync(const PttaStatSync* sy, float* g, long n, hipStream_t s);                          // gbn.hip: mean over the ranks
 
-// ---- heads.hip --------------------------------------------------------------------------------
+// ---- heads.hip (packers, ptta_launch_gemm), heads_f32 / heads_x3 / heads_ws.hip (its kernels), heads_bn.hip (moments, BatchNorm1d) ----
 struct GemmArgs {
     const void* A = nullptr; int a_bf16 = 0;   // [R][K] (fp32, or bf16 NHWC features when a_bf16)
     const float* A2 = nullptr;                 // second A tensor (h1) for the BN-backward prologue
@@ -171,7 +171,7 @@ void ptta_pack_w0_frag(const float* W0, void* frag, hipStream_t s);
 int ptta_head_moment_blocks(long R);
 int ptta_launch_head_moments(const float* X, long R, int npass, const float* W0, const float* b0, float* part, hipStream_t s);
 // after the epi-3 GEMM + ptta_launch_bn_bwd_finalize: dX = P[0] + P[1] - X M - u (M, u from the BatchNorm-backward means, derived per block in fp64)
-// halves: P holds 2 column-block halves (heads.hip EPI 3) or 1 (heads_n.hip); dX_bf16: the gradient map is narrow
+// halves: P holds 2 column-block halves (heads_ws.hip EPI 3) or 1 (heads_n.hip); dX_bf16: the gradient map is narrow
 int ptta_launch_head_bwd_finish(const double* k12, const float* W0, const float* P, const float* X, long R, void* dX, hipStream_t s, int halves = 2, int dX_bf16 = 0);
 void ptta_split_weight(const float* w, bf16_t* hi, bf16_t* lo, bf16_t* il, long n, int K, hipStream_t s);
 int ptta_gemm_row_blocks(int R);
@@ -209,7 +209,7 @@ void ptta_hn_pack_w(const bf16_t* w_hi_rowmajor, bf16_t* w_slice_major, int K, h
 int ptta_launch_hn_untile(const void* src_tiled, float* dst, long R, hipStream_t s);
 int ptta_hn_moment_blocks(long R);
 long ptta_hn_moment_scratch(long R);       // doubles of scratch per pass
-struct HnBnOut {                 // what bn_finalize_kernel (heads.hip) writes: with `mean` set the stats kernel finalises the BatchNorm itself
+struct HnBnOut {                 // what bn_finalize_kernel (heads_bn.hip) writes: with `mean` set the stats kernel finalises the BatchNorm itself
     const float *gamma = nullptr, *beta = nullptr; float eps = 1e-5f, momentum = 0.1f;
     float *rm = nullptr, *rv = nullptr; long long* nbt = nullptr;
     float *mean = nullptr, *inv = nullptr, *scale = nullptr, *shift = nullptr;
