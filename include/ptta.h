@@ -405,6 +405,31 @@ int ptta_ingest_raw(const uint8_t* image_u8, const uint16_t* sparse_u16, const u
                     float* validity_out, float* gt_out, float* gt_validity_out, int n, int src_height, int src_width, int height, int width,
                     const int32_t* start_y, const int32_t* start_x, float multiplier, ptta_stream s);
 
+/* Raw-frame egress on device, the inverse of ptta_ingest_raw: the reference's writers' arithmetic and the paste back into the stored frame
+ * in one pass, so that 2 bytes per pixel (2 + 2 + 3 with validity and image) cross the host link instead of 4 (4 + 4 + 12).  depth and
+ * validity are N x 1 x height x width fp32, image is N x 3 x height x width fp32, all on the device:
+ *   depth_u16[b, sy+y, sx+x]    = p > 0 ? (uint16) min(trunc(p), 65535) : 0, p = depth[b,0,y,x] * multiplier (one fp32 multiply)
+ *                                                                        save_depth: np.uint32(z * multiplier) as a 16-bit PNG
+ *                                                                        (src/data_utils.py:236-251)
+ *   validity_u16[b, sy+y, sx+x] = validity[b,0,y,x] > 0 ? 256 : 0        save_validity_map (:283-298)
+ *   image_u8[b, sy+y, sx+x, c]  = q > 0 ? (uint8) min(trunc(q), 255) : 0, q = image[b,c,y,x] * image_scale (one fp32 multiply; 255 for
+ *                                                                        normalized=True, 1 for False)
+ *                                                                        save_image(..., data_format='CHW') (:29-78)
+ * Outputs are N x dst_height x dst_width uint16 and N x dst_height x dst_width x 3 uint8, the stored frame; the input lands in the window
+ * [sy : sy+height, sx : sx+width] of its sample and every output element outside it is written 0: the caller never clears an output.
+ * start_y / start_x are int32, device, per sample (NULL = 0), clamped into the sample exactly as ptta_ingest_raw and ptta_crop_flip clamp
+ * them.  Where the reference is defined (0 <= p < 2^31, 0 <= q < 256) the bits are its own: it truncates, and Pillow stores 65535 for
+ * everything at or above 65536.  Outside that range its result is an accident of casts and this library defines it: a negative value, -0
+ * and NaN give 0; anything at or above the top of the range, +inf included, gives 65535 (255 for the image, where the reference wraps).
+ * NaN validity gives 0.  Each input may be NULL together with its output.  -22 before any launch, with the reason in
+ * ptta_last_error(NULL): no input at all, an input without its output or an output without its input, n < 1, a size < 1,
+ * height > dst_height or width > dst_width, a multiplier or image_scale that is not a positive finite number, an odd depth_u16 or
+ * validity_u16 address.  Every output byte is written exactly once, 16-bit rows with 16-byte stores laid on the destination's alignment,
+ * and no byte outside the inputs is read; results are bit-identical from run to run.  Handle-free, one launch, enqueues only. */
+int ptta_egress_raw(const float* depth, const float* validity, const float* image, uint16_t* depth_u16, uint16_t* validity_u16,
+                    uint8_t* image_u8, int n, int height, int width, int dst_height, int dst_width, const int32_t* start_y,
+                    const int32_t* start_x, float multiplier, float image_scale, ptta_stream s);
+
 /* Eval-time hole filling on device (src/nlspn_model_adapt.py:124-127; the definition is proxytta/inpaint.py, the scipy restatement of
  * skimage.restoration.inpaint_biharmonic): per sample of the N x 1 x height x width fp32 map `depth`, the exact zeros are the unknowns of
  * the biharmonic system the host code builds (radius-2 box clipped to the image, Laplacian with replicated box edges, known pixels on the

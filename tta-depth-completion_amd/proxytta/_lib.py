@@ -157,6 +157,7 @@ SIGNATURES = [
     ('ptta_head_set_form', c_int, [_P, c_int]),
     ('ptta_crop_flip', c_int, [_P, _P] + [c_int] * 6 + [_P] * 5),
     ('ptta_ingest_raw', c_int, [_P] * 8 + [c_int] * 5 + [_P, _P, c_float, _P]),
+    ('ptta_egress_raw', c_int, [_P] * 6 + [c_int] * 5 + [_P, _P, c_float, c_float, _P]),
     ('ptta_inpaint_scratch_bytes', c_int64, [c_int, c_int, c_int, c_int]),
     ('ptta_inpaint_biharmonic', c_int, [_P, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, _P, c_int64, _P, _P]),
     ('ptta_summary_grid_shape', c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),

@@ -817,17 +817,22 @@ class ExternalModel_Adapt(object):
         """One TTA step (src/tta_main.py:610-633) in one library call; returns (loss_info[4], depth).  next_frame: see the adapter's step."""
         return self.model.step(image, sparse_depth, validity_map, loss_image, want_depth, next_frame=next_frame)
 
-    def adapt(self, image, sparse_depth, inner_iter=1, validity_map=None, loss_image=None, next_frame=None, ground_truth=None, score=None):
+    def adapt(self, image, sparse_depth, inner_iter=1, validity_map=None, loss_image=None, next_frame=None, ground_truth=None, score=None,
+              sink=None, sink_paths=None):
         """Per-frame adaptation = inner_iter steps then the scored eval forward
         (src/tta_main.py:579-636 and :729-736).  Returns (depth, loss_info of the last step).
         next_frame = (image, sparse_depth) the next call will pass: announced to the LAST step of this frame (frame pipelining).
         ground_truth and score (a proxytta.score.RunScore), given together: score.update(depth, ground_truth) is enqueued behind the scored
-        forward on the same stream (src/tta_main.py:769-798 without its copy to the host); the return value is the same."""
+        forward on the same stream (src/tta_main.py:769-798 without its copy to the host); the return value is the same.
+        sink (a proxytta.sink.RawFrameSink): sink.submit(depth=depth, paths=sink_paths) is enqueued behind the scored forward (behind the
+        score's update when there is one): the prediction leaves as the 16-bit map save_depth stores; the return value is the same."""
         if (ground_truth is None) != (score is None):
             raise ValueError('adapt: ground_truth and score are given together or not at all')
         depth, info = self._adapt(image, sparse_depth, inner_iter, validity_map, loss_image, next_frame)
         if score is not None:
             score.update(depth, ground_truth)
+        if sink is not None:
+            sink.submit(depth=depth, paths=sink_paths)
         return depth, info
 
     def _adapt(self, image, sparse_depth, inner_iter, validity_map, loss_image, next_frame):
