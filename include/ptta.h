@@ -652,7 +652,7 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  * handle's streams and drops its captured graphs; the next step re-captures.  Every non-default value is a correct, slower form of
  * the same step, kept as the check of the default (tests/test_gpu_options.py) or taken by the library itself where the default
  * form does not apply (small maps, N > 16, SyncBatchNorm exchange).  Unknown key / value out of range: -22; a key the handle does
- * not have: -38 (the generic engine has "graph", "head_bn_fused" and, on PTTA_ADAPT_META_ONLY handles, "eval_bn_fused"; PTTA_DTYPE_MIXED handles keep every key but graph / aux_stream / thru / adam_in_wgrad / pair_fuse / tpair_fuse at 1).
+ * not have: -38 (the generic engine has "graph", "head_bn_fused", on NLSPN handles that train "deterministic" and, on PTTA_ADAPT_META_ONLY handles, "eval_bn_fused"; PTTA_DTYPE_MIXED handles keep every key but graph / aux_stream / thru / adam_in_wgrad / pair_fuse / tpair_fuse at 1).
  *   key             default  meaning of 0
  *   "graph"         0        (1:) ptta_step / ptta_step_pipelined / ptta_forward_eval replay captured hipGraphs from their second call on.  Default
  *                            since round 5: direct launches on the caller's stream and the handle's own streams -- measured FASTER than replay
@@ -707,6 +707,31 @@ int ptta_set_graph(ptta_handle h, int enable);         /* = ptta_set_option(h, "
  *                            tools/bench_head_generic.py): NLSPN 352x1216 9.49 against 10.63 ms (N 1), 17.47 against 19.66 (N 2); CostDCNet 480x640
  *                            4.94 against 5.42 (N 1), 8.31 against 9.21 (N 2); 0 equals the step before the option within the run-to-run spread.
  *                            Faster on both backbones, hence 1 on both
+ *   "deterministic" 0        (NLSPN handles with a backward: 1layer, 2layers, PTTA_ADAPT_META_ONLY, PTTA_META_NONE, PTTA_NLSPN_SYNCBN_ADAPT, both dtypes;
+ *                            -38 with a reason on MSG_CHN and CostDCNet, whose steps are bit-reproducible as they are,
+ *                            and on the source model PTTA_META_NONE | PTTA_ADAPT_META_ONLY, which has no backward)  0: the 18 propagation
+ *                            sweeps' feature gradient and the affinity gradient's confidence gradient are scattered with float atomicAdd (LDS +
+ *                            global): the order the atomics arrive in decides the rounding, two runs of one build differ by ~5e-6 relative in the
+ *                            gradients.  1: the same two scatters add 64-bit FIXED-POINT integers instead (ds_add_u64 on the LDS tile, 64-bit
+ *                            global atomics), llrintf(contribution * 2^S), and a convert launch per scatter turns the int64 map into fp32.
+ *                            Integer addition is associative: the same frames give the same bits on every run, direct launches or graph replay.
+ *                            S is chosen on the device, per launch, so that overflow is impossible: 2^S * (bound of the sum of |contributions|)
+ *                            <= 2^60, the bound being N*H*W * max|gout| * max_pixel(sum_k |affinity_k|) for a sweep and 8 * N*H*W * max|g_c| for
+ *                            the confidence gradient, each maximum reduced on the device with integer atomicMax on the fp32 bit patterns (no host
+ *                            read: the step stays capturable) and rounded up to a power of two.  Quantum: 2^-S, at most 2^-57 of that bound
+ *                            (N*H*W = 2^20, affinities summing to 3: below 2^-34 of max|gout|).  Per element: every contribution is rounded by
+ *                            at most half a quantum, then the sum is rounded ONCE to fp32 -- |error| <= K * 2^-S / 2 + 2^-24 |sum| for K
+ *                            contributions, where the float form rounds by up to 2^-24 of the running sum at each of its K additions in an
+ *                            arbitrary order.  A maximum of 0 gives a zero map; a non-finite maximum (inf or NaN anywhere in gout, the
+ *                            affinities or g_c) gives a map of NaN in every element, where the float form spreads it sweep by sweep.  The gathers
+ *                            (offset and tap-affinity gradients, the g_oa channels) keep their arithmetic bit for bit
+ *                            (tests/test_gpu_nlspn_det_elementwise.py).  Memory: 8 bytes per pixel of the batch + 256 bytes, allocated when the
+ *                            option is first set to 1.  Not bit-identical to 0 by construction; same error class (the tests hold 1 to twice the
+ *                            measured error of 0 against an fp64 reference).  Measured on MI355X, 352x1216, 1 against 0 alternating in one
+ *                            process (profiles/nlspn_deterministic.txt, tools/bench_nlspn_deterministic.py): 21.75 against 20.26 ms per step
+ *                            (N 1, fp32), 20.98 against 19.54 (N 1, mixed), 40.68 against 37.43 (N 2, fp32), 39.06 against 35.92 (N 2, mixed);
+ *                            one sweep's gradient 140 against 74 us (the 64-bit LDS atomic runs at about half the rate of the float one);
+ *                            0 equals the step before the option within the run-to-run spread.  Slower, hence 0
  * Read-only keys (ptta_get_option; -22 from ptta_set_option):
  *   "pipelined_active"  1 when ptta_step_pipelined runs as itself on this handle as configured now; 0 when it degrades to ptta_step call by call
  *                       (generic-engine backbones, the dual-corner padded path, a statistics exchange or a gradient communicator bound,
@@ -1006,6 +1031,21 @@ typedef struct ptta_loss_args {
     float* loss_info; float* rowstats; float* gdepth; float* gref; float* coef;
 } ptta_loss_args;
 int ptta_op_loss(const ptta_loss_args* a, ptta_stream s);
+/* Test hooks: NLSPN's propagation gradients stand-alone, in both forms (csrc/nlspn_prop.hip; option "deterministic").  Planar fp32 device maps:
+ * pinned, fix, gout, gfeat [b][h*w]; off9, goff9 [b][18][h*w]; aff9, gaff9 [b][9][h*w].  form 0: the float-atomic kernels of the default step;
+ * form 1: the fixed-point forms, with the maxima their scale comes from reduced from aff9 and gout first, as the engine's backward does.
+ * scratch: ptta_nl_det_scratch_bytes(b, h, w) bytes of device memory, 8-byte aligned (form 1; form 0 takes NULL) -- 256 + 8 * b * h * w.
+ * ptta_op_nl_prop_bwd: ONE sweep's gradient: gfeat is overwritten, goff9 and gaff9 are accumulated into (the engine adds 18 sweeps).  reps > 0:
+ * `reps` more launches of the sweep (form 0: its memset and kernel; form 1: scatter and convert) timed with hipEvents on s, microseconds per
+ * sweep to *us_per_call_host -- goff9 / gaff9 keep accumulating.  ptta_op_nl_affinity_bwd: oa and goa are CONTIGUOUS NHWC maps of 24 channels
+ * (o1 | o2 | aff), aff_scale one device float (prop_layer.aff_scale_const), legacy 0 / 1 (PTTA_NLSPN_LEGACY_OFFSET); goa and gconf [b][h*w] are
+ * overwritten.  Both synchronise. */
+int64_t ptta_nl_det_scratch_bytes(int b, int h, int w);
+int ptta_op_nl_prop_bwd(const float* pinned, const float* fix, const float* off9, const float* aff9, const float* gout, float* gfeat,
+                        float* goff9, float* gaff9, int b, int h, int w, int form, void* scratch, int reps, float* us_per_call_host,
+                        ptta_stream s);
+int ptta_op_nl_affinity_bwd(const float* oa_nhwc, const float* conf, const float* aff_scale, int legacy, const float* goff9, const float* gaff9,
+                            float* goa_nhwc, float* gconf, int b, int h, int w, int form, void* scratch, ptta_stream s);
 /* Diagnostic (tools/bench_chain.py): `reps` dependent launches of one stride-1 32->32 convolution (fp32 NHWC, default arithmetic) captured
  * into one hipGraph and replayed `replays` times: microseconds per launch INSIDE a replayed graph.  epi_flags: 2 = ReLU mask from `aux`,
  * 4 = skip addition of `aux`, 8 = the same chain launched directly (no graph), 16 = the layer loop (ONE launch per `reps` layers with a

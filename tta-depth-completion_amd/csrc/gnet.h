@@ -317,6 +317,9 @@ struct GNet {
     int head_get_grad(const char* name, float* dst, int64_t capacity, int* has_grad_host, hipStream_t s);
     int head_sync_packed(bool targets_too, hipStream_t s);
     virtual int debug_extra(const std::string& nm, const float** src, long* n) { (void)src; (void)n; return fail("unknown debug tensor " + nm, -2); }
+    // option "deterministic" (include/ptta.h): NLSPN's propagation gradients without float atomics; the other backbones' steps are bit-reproducible already
+    virtual int set_deterministic(int v) { (void)v; return fail("ptta_set_option: 'deterministic' belongs to NLSPN handles (this backbone's step is bit-reproducible as it is)", -38); }
+    virtual int get_deterministic(int* v) { (void)v; return -38; }
 
     int fail(const std::string& m, int code) { err = m; return code; }
     void* dalloc(size_t bytes) {

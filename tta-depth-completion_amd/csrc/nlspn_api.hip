@@ -276,8 +276,25 @@ struct nlspn_engine : GNet {
         else return fail("unknown debug tensor " + nm, -2);
         return 0;
     }
+    // option "deterministic": backward takes the fixed-point forms of nlspn_prop.hip for the 18 sweeps and the affinity gradient.  Their
+    // workspace (8 bytes per pixel of the batch + the maxima) is allocated when the option is first set to 1, never at create
+    int deterministic = 0;
+    unsigned* det_mx = nullptr; unsigned long long* det_acc = nullptr;
+    int set_deterministic(int v) override {
+        if (!no_train_why.empty()) return fail("ptta_set_option: 'deterministic' belongs to handles with a backward -- " + no_train_why, -38);
+        if (v < 0 || v > 1) return fail("ptta_set_option: value out of range for 'deterministic'", -22);
+        if (v && !det_mx) {
+            char* ws = (char*)dalloc(ptta_nl_det_ws_bytes(N, H, W));
+            if (!ws) { oom = false; return fail("ptta_set_option: out of device memory for the workspace of 'deterministic'", -12); }
+            det_mx = (unsigned*)ws; det_acc = (unsigned long long*)(ws + PTTA_NL_DET_SLOTS * sizeof(unsigned));
+        }
+        if (v != deterministic) { drop_graphs(); deterministic = v; }
+        return 0;
+    }
+    int get_deterministic(int* v) override { if (!no_train_why.empty()) return -38; *v = deterministic; return 0; }
     int forward(const float* image, const float* sparse, bool train, hipStream_t s) override;
     int backward(hipStream_t s) override;
+    int backward_prop_det(hipStream_t s);
     int stage_inputs_nhwc(const float* image, const float* sparse, bool train, hipStream_t s);
     // stage-2 head trainer (ghead.hip): rows = fe6 of the real pass / of the zero-image pass (nlspnmodel_adapt.py:1028-1046); MLP(512, 1024, 1024)
     int head_spec(HeadSpec* hs) override {
@@ -336,6 +353,7 @@ int nlspn_engine::backward(hipStream_t s) {
     hipLaunchKernelGGL(clamp_bwd_kernel, dim3(nb(NP)), dim3(256), 0, s, gdepth, feats + (size_t)PROP_TIME * NP, gy, NP);
     if (hipMemsetAsync(goff9, 0, (size_t)NP * 18 * sizeof(float), s) != hipSuccess) return fail("memset failed", -5);
     if (hipMemsetAsync(gaff9, 0, (size_t)NP * 9 * sizeof(float), s) != hipSuccess) return fail("memset failed", -5);
+    if (deterministic) { const int rc = backward_prop_det(s); return rc ? rc : run_ops_bwd(s); }
     float* gcur = gy; float* gnext = gping;
     for (int k = PROP_TIME - 1; k >= 0; --k) {
         float* dst = k == 0 ? T[t_pred].g : gnext;
@@ -348,6 +366,27 @@ int nlspn_engine::backward(hipStream_t s) {
     if (ptta_launch_nl_affinity_bwd(view(t_oa, W_GRAD, true), T[t_conf].p, S, legacy, goff9, gaff9, view(t_oa, W_GRAD, true, true), T[t_conf].g, s))
         return fail("affinity gradient failed", -5);
     return run_ops_bwd(s);
+}
+
+// the same sweeps and affinity gradient with the scatters in fixed point (no float atomic, no memset of the targets: the convert launches
+// overwrite them).  Maxima: det_mx[0] = max sum|aff9|, det_mx[1 + i] = max|gout| of the i-th sweep run (written by the sweep before it, the
+// first by a reduction over gy), det_mx[PROP_TIME + 2] = max|g_c| of the affinity gradient.
+int nlspn_engine::backward_prop_det(hipStream_t s) {
+    const long NP = (long)N * H * W;
+    if (hipMemsetAsync(det_mx, 0, ptta_nl_det_ws_bytes(N, H, W), s) != hipSuccess) return fail("memset failed", -5);     // maxima and the int64 map
+    if (ptta_launch_nl_affsum_max(aff9, N, H, W, det_mx, s) || ptta_launch_nl_absmax(gy, NP, det_mx + 1, s)) return fail("propagation gradient failed", -5);
+    float* gcur = gy; float* gnext = gping;
+    for (int k = PROP_TIME - 1, i = 0; k >= 0; --k, ++i) {
+        float* dst = k == 0 ? T[t_pred].g : gnext;
+        if (ptta_launch_nl_prop_bwd_det(feats + (size_t)k * NP, T[t_sd].p, off9, aff9, gcur, dst, goff9, gaff9, N, H, W, det_acc, det_mx, det_mx + 1 + i,
+                                        k > 0 ? det_mx + 2 + i : nullptr, s))
+            return fail("propagation gradient failed", -5);
+        float* t = gcur; gcur = dst; gnext = t;
+    }
+    if (ptta_launch_nl_affinity_bwd_det(view(t_oa, W_GRAD, true), T[t_conf].p, S, legacy, goff9, gaff9, view(t_oa, W_GRAD, true, true), T[t_conf].g, det_acc,
+                                        det_mx + PROP_TIME + 2, s))
+        return fail("affinity gradient failed", -5);
+    return 0;
 }
 
 GNet* nlspn_create(int n, int h, int w, const ptta_hparams* hp, int legacy_offset, int* rc) {

@@ -8,7 +8,9 @@
 //   nl_prop_fwd     : one propagation sweep: re-impose the sparse input (:362-364) while sampling, 9 bilinear taps,
 //   nl_prop_bwd     : its gradient (tap-affinity and offset gradients as gathers, feature gradient as a scatter
 //                     of float atomics like the reference's col2im, modulated_deform_im2col_cuda.cuh:197-254),
-//   nl_affinity_bwd : gradient of the fused affinity pass wrt the conv output and the confidence map.
+//   nl_affinity_bwd : gradient of the fused affinity pass wrt the conv output and the confidence map (the latter again a float-atomic scatter),
+//   nl_prop_bwd_det / nl_affinity_bwd_det : the same two gradients with the scatters in 64-bit fixed point -- integer atomics, a scale chosen on
+//                     the device from the actual maxima, one convert launch each: bit-reproducible (ptta_set_option "deterministic").
 // Layouts: feature / confidence / sparse maps planar [B][H*W]; off9 [B][18][H*W] (h,w per tap), aff9 [B][9][H*W]
 // (the reference's NCHW offset / mask tensors: consecutive lanes read consecutive addresses);
 // the conv output is a strided NHWC view with 24 channels (o1 | o2 | aff as torch.chunk sees them, :259-260).
@@ -298,6 +300,233 @@ __global__ __launch_bounds__(256) void nl_affinity_bwd_kernel(GView oa, const fl
     }
 }
 
+// ---- the deterministic forms (ptta_set_option "deterministic") ------------------------------------------------------------------------
+// Both scatters above add floats in whatever order the atomics arrive, and float addition is not associative.  Here every contribution
+// is converted to a 64-bit fixed-point integer, llrintf(val * 2^S), and added with INTEGER atomics (ds_add_u64 on the LDS tile,
+// global_atomic_add_x2 for the flush and beyond the apron): integer addition is associative, so the sum is the same bits in every
+// order; one convert launch turns the int64 map into fp32 (and zeroes it for the next use).  S is chosen on the device, per launch, from
+// bounds on the actual values, themselves reduced with integer atomicMax on the fp32 bit patterns of |x| (integer order = float order
+// for non-negative floats, and max is order-independent):
+//   sweep:    sum over all contributions of |val| <= N*H*W * max|gout| * max_pixel(sum_k |aff9_k|)   (bilinear weights sum to <= 1 per tap)
+//   affinity: sum |val| <= 8 * N*H*W * max|g_c|
+// With x < 2^e(x) read from the exponent field, S = 60 - e(max..) [- e(max..)] - ceil(log2(N*H*W)) [- 3] keeps the sum of magnitudes below
+// 2^60; the two spare bits cover the fp32 rounding of the products and the half quantum each llrintf may add.  Nothing can overflow, for
+// any input.  A maximum of 0 gives S large and a zero map; a non-finite maximum (bits >= 0x7f800000: inf or NaN somewhere in gout, aff9 or
+// g_c) makes the convert launch write NaN over the whole map -- the float form would have spread it by a few pixels per sweep instead.
+// Quantum 2^-S: between 2^-60 and 2^-57 of the bound of the sum (each maximum is rounded up to a power of two).  Every contribution is
+// rounded by at most half of it, far below the fp32 rounding of the float form's partial sums (2^-24 of the running sum per addition); the
+// convert launch rounds ONCE to fp32 (include/ptta.h states the bound).
+__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+// v < 2^det_exp(bits of |v|) for every finite v (denormals: exponent field 0 -> 2^-126)
+__device__ __forceinline__ int det_exp(unsigned bits) { return (int)(bits >> 23) - 126; }
+struct DetScale { int S; bool bad; };
+__device__ __forceinline__ DetScale det_scale(const unsigned* __restrict__ ma, const unsigned* __restrict__ mb, int nbits) {
+    const unsigned a = ma[0], b = mb ? mb[0] : 0u;
+    DetScale d;
+    d.bad = a >= 0x7f800000u || b >= 0x7f800000u;
+    d.S = 60 - nbits - det_exp(a) - (mb ? det_exp(b) : 0);
+    return d;
+}
+// max over the block of `m`, one integer atomicMax per wave
+__device__ __forceinline__ void det_max_commit(unsigned m, unsigned* __restrict__ slot) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)m, o); m = t > m ? t : m; }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(slot, m);
+}
+__global__ __launch_bounds__(256) void nl_absmax_kernel(const float* __restrict__ x, long n, unsigned* __restrict__ slot) {
+    unsigned m = 0;
+    for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long)gridDim.x * blockDim.x) { const unsigned t = abs_bits(x[k]); m = t > m ? t : m; }
+    det_max_commit(m, slot);
+}
+// max over the pixels of sum_k |aff9_k|: what one unit of gout can scatter from one pixel
+__global__ __launch_bounds__(256) void nl_affsum_max_kernel(const float* __restrict__ aff9, int B, long P, unsigned* __restrict__ slot) {
+    unsigned m = 0;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < (long)B * P; idx += (long)gridDim.x * blockDim.x) {
+        const float* a = aff9 + (idx / P) * 9 * P + idx % P;
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) s += fabsf(a[(long)k * P]);
+        const unsigned t = abs_bits(s); m = t > m ? t : m;
+    }
+    det_max_commit(m, slot);
+}
+// int64 fixed point -> fp32, the map zeroed for its next use; m_next (may be null) receives max|out| for the sweep that reads `out` as its gout
+__global__ __launch_bounds__(256) void nl_det_convert_kernel(unsigned long long* __restrict__ acc, float* __restrict__ out, long n,
+                                                             const unsigned* __restrict__ ma, const unsigned* __restrict__ mb, int nbits,
+                                                             unsigned* __restrict__ m_next) {
+    const DetScale d = det_scale(ma, mb, nbits);
+    unsigned m = 0;
+    for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long)gridDim.x * blockDim.x) {
+        const long long q = (long long)acc[k];
+        if (q) acc[k] = 0ull;
+        const float v = d.bad ? __uint_as_float(0x7fc00000u) : ldexpf((float)q, -d.S);
+        out[k] = v;
+        const unsigned t = abs_bits(v); m = t > m ? t : m;
+    }
+    if (m_next) det_max_commit(m, m_next);
+}
+
+// nl_prop_bwd_kernel with the scatter in fixed point.  Everything up to the scatter is that kernel's text, so goff9 / gaff9 -- gathers, the same
+// thread every sweep -- keep their arithmetic (tests/test_gpu_nlspn_det_elementwise.py holds the two forms bitwise equal there); the neighbour
+// merging stays too: it adds the same two lanes' floats whenever their cell indices match, a function of the inputs alone.
+__global__ __launch_bounds__(256, 4) void nl_prop_bwd_det_kernel(const float* __restrict__ pinned, const float* __restrict__ fix,
+                                                              const float* __restrict__ off9, const float* __restrict__ aff9,
+                                                              const float* __restrict__ gout, unsigned long long* __restrict__ acc,
+                                                              float* __restrict__ goff9, float* __restrict__ gaff9, int B, int H, int W,
+                                                              const unsigned* __restrict__ m_aff, const unsigned* __restrict__ m_g, int nbits) {
+    __shared__ unsigned long long tile[PB_W * PB_W];
+    const long P = (long)H * W;
+    const int ntx = (W + PB_T - 1) / PB_T, nty = (H + PB_T - 1) / PB_T;
+    const int b = blockIdx.x / (ntx * nty), tr = blockIdx.x % (ntx * nty);
+    const int ty0 = (tr / ntx) * PB_T, tx0 = (tr % ntx) * PB_T;
+    for (int k = threadIdx.x; k < PB_W * PB_W; k += 256) tile[k] = 0ull;
+    __syncthreads();
+    const DetScale ds = det_scale(m_aff, m_g, nbits);
+    const int y = ty0 + (threadIdx.x >> 4), x = tx0 + (threadIdx.x & 15);
+    const float* fb = pinned + (long)b * P; const float* xb = fix + (long)b * P;
+    unsigned long long* gb = acc + (long)b * P;
+    const bool inimg = y < H && x < W;
+    const int col = threadIdx.x & 15, wrow = (threadIdx.x >> 4) & 3;            // position inside the wave's 4 x 16 pixel patch
+    {
+        const long pix = (long)min(y, H - 1) * W + min(x, W - 1), idx = (long)b * P + pix;
+        const float* o = off9 + (long)b * 18 * P + pix; const float* a = aff9 + (long)b * 9 * P + pix;
+        float* go = goff9 + (long)b * 18 * P + pix; float* ga = gaff9 + (long)b * 9 * P + pix;
+        const float g = gout[idx];
+        float ov[18], av[9];
+#pragma unroll
+        for (int k = 0; k < 18; ++k) ov[k] = o[(long)k * P];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) av[k] = a[(long)k * P];
+#pragma unroll
+        for (int k0 = 0; k0 < 9; k0 += 3) {
+            TapG t[3];
+            float v[3][4], m[3][4], gov[6], gav[3];
+#pragma unroll
+            for (int kk = 0; kk < 3; ++kk) {
+                const int k = k0 + kk;
+                gov[2 * kk] = go[(long)(2 * k) * P]; gov[2 * kk + 1] = go[(long)(2 * k + 1) * P]; gav[kk] = ga[(long)k * P];
+                t[kk] = tap_geom(H, W, (float)(y + k / 3 - 1) + ov[2 * k], (float)(x + k % 3 - 1) + ov[2 * k + 1]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { v[kk][j] = fb[t[kk].q[j]]; m[kk][j] = xb[t[kk].q[j]]; }
+            }
+#pragma unroll
+            for (int kk = 0; kk < 3; ++kk) {
+                const int k = k0 + kk;
+                const TapG& tk = t[kk];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (!tk.ok[j]) v[kk][j] = 0.f;
+                const float hh = 1.f - tk.lh, hw = 1.f - tk.lw, ga_ = g * av[k];
+                if (inimg) {
+                    ga[(long)k * P] = gav[kk] + g * tap_blend(tk, v[kk]);
+                    go[(long)(2 * k) * P] = gov[2 * kk] + ga_ * (-hw * v[kk][0] - tk.lw * v[kk][1] + hw * v[kk][2] + tk.lw * v[kk][3]);
+                    go[(long)(2 * k + 1) * P] = gov[2 * kk + 1] + ga_ * (-hh * v[kk][0] + hh * v[kk][1] - tk.lh * v[kk][2] + tk.lh * v[kk][3]);
+                }
+                float val[4] = {hh * hw * ga_, hh * tk.lw * ga_, tk.lh * hw * ga_, tk.lh * tk.lw * ga_};
+                bool act[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { act[j] = inimg && tk.ok[j] && !(m[kk][j] > 0.f) && val[j] != 0.f; if (!act[j]) val[j] = 0.f; }
+                auto merge = [&](int src, int dst, bool horizontal) __attribute__((always_inline)) {
+                    const int sq = act[src] ? tk.q[src] : -1;
+                    int nq, rsq; float rv;
+                    if (horizontal) {
+                        nq = __builtin_amdgcn_update_dpp(0, tk.q[dst], 0x101, 0xf, 0xf, true);                        // row_shl:1 -> lane + 1
+                        rsq = __builtin_amdgcn_update_dpp(-1, sq, 0x111, 0xf, 0xf, false);                             // row_shr:1 -> lane - 1
+                        rv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(val[src]), 0x111, 0xf, 0xf, true));
+                    } else {
+                        nq = __shfl_down(tk.q[dst], 16); rsq = __shfl_up(sq, 16); rv = __shfl_up(val[src], 16);
+                    }
+                    const bool edge_s = horizontal ? col == 15 : wrow == 3, edge_r = horizontal ? col == 0 : wrow == 0;
+                    const bool give = !edge_s && sq >= 0 && nq == sq;
+                    const bool take = !edge_r && rsq >= 0 && rsq == tk.q[dst];
+                    if (take) { val[dst] += rv; act[dst] = true; }
+                    if (give) { act[src] = false; val[src] = 0.f; }
+                };
+                merge(1, 0, true); merge(3, 2, true);
+                merge(2, 0, false); merge(3, 1, false);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!act[j] || ds.bad) continue;
+                    const unsigned long long q = (unsigned long long)llrintf(ldexpf(val[j], ds.S));
+                    if (!q) continue;
+                    const int qy = tk.q[j] / W, qx = tk.q[j] - qy * W;
+                    const int ly = qy - ty0 + PB_R, lx = qx - tx0 + PB_R;
+                    if (ly >= 0 && ly < PB_W && lx >= 0 && lx < PB_W) atomicAdd(&tile[ly * PB_W + lx], q);
+                    else atomicAdd(gb + tk.q[j], q);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < PB_W * PB_W; k += 256) {
+        const unsigned long long v = tile[k];
+        if (!v) continue;
+        const int qy = ty0 - PB_R + k / PB_W, qx = tx0 - PB_R + k % PB_W;
+        if (qy >= 0 && qy < H && qx >= 0 && qx < W) atomicAdd(gb + qy * W + qx, v);
+    }
+}
+
+// nl_affinity_bwd_kernel in two passes, because the scattered g_c is only known inside the kernel: PASS 0 writes g_oa (that kernel's text:
+// same arithmetic) and reduces max|g_c|; PASS 1 computes g_c again and scatters it in fixed point at the scale the maximum allows.  The
+// recomputation costs one more affinity pass per step (the sweeps run 18) and spares a 32-byte-per-pixel scratch of g_c.
+template <int PASS>
+__global__ __launch_bounds__(256) void nl_affinity_bwd_det_kernel(GView oa, const float* __restrict__ conf, const float* __restrict__ Sp,
+                                                                  int legacy, const float* __restrict__ goff9, const float* __restrict__ gaff9,
+                                                                  GView goa, unsigned long long* __restrict__ acc, unsigned* __restrict__ m_gc, int nbits) {
+    const int H = oa.H, W = oa.W;
+    const long P = (long)H * W, total = (long)oa.B * P;
+    const float S = Sp[0];
+    DetScale ds; ds.S = 0; ds.bad = false;
+    if (PASS == 1) { ds = det_scale(m_gc, nullptr, nbits); if (ds.bad) return; }
+    unsigned mx = 0;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(idx / P); const long pix = idx % P;
+        const int y = (int)(pix / W), x = (int)(pix % W);
+        float v[24];
+        const float* src = oa.p + idx * oa.ld;
+#pragma unroll
+        for (int k = 0; k < 24; ++k) v[k] = src[k];
+        AffPix r;
+        aff_forward_pixel(v, conf + (long)b * P, H, W, y, x, S, legacy, r);
+        const float* go = goff9 + (long)b * 18 * P + pix; const float* ga = gaff9 + (long)b * 9 * P + pix;
+        float* dst = goa.p + idx * goa.ld;
+        float G[8], dot = 0.f;
+#pragma unroll
+        for (int n = 0; n < 8; ++n) { G[n] = ga[(long)tap_of_pair(n) * P] - ga[4 * P]; dot += G[n] * (r.a[n] / r.sp); }
+        const bool through = !(r.s < 1.f);
+        unsigned long long* gcb = acc + (long)b * P;
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+            const int k = tap_of_pair(n);
+            float g_a = G[n] / r.sp;
+            if (through) g_a -= dot / r.sp * (r.a[n] > 0.f ? 1.f : (r.a[n] < 0.f ? -1.f : 0.f));
+            const float g_t = g_a * r.c[n], g_c = g_a * r.t[n];
+            if (PASS == 0) {
+                const float th = r.t[n] * (S + 1e-8f);                    // tanh(raw)
+                dst[16 + n] = g_t * (1.f - th * th) / (S + 1e-8f);
+                dst[2 * n] = go[(long)(2 * k) * P]; dst[2 * n + 1] = go[(long)(2 * k + 1) * P];
+                const unsigned t = abs_bits(g_c); mx = t > mx ? t : mx;
+                continue;
+            }
+            float oh = v[2 * n], ow = v[2 * n + 1];
+            if (legacy) { oh += (float)(k / 3) - 1.f; ow += (float)(k % 3) - 1.f; }
+            const Corner c = corner_of((float)y + oh, (float)x + ow, H, W);
+            if (c.inside) {
+                const int h1 = c.h0 + 1, w1 = c.w0 + 1;
+                const float hh = 1.f - c.lh, hw = 1.f - c.lw;
+                auto put = [&](int q, float val) __attribute__((always_inline)) {
+                    const unsigned long long f = (unsigned long long)llrintf(ldexpf(val, ds.S));
+                    if (f) atomicAdd(gcb + q, f);
+                };
+                if (c.h0 >= 0 && c.w0 >= 0) put(c.h0 * W + c.w0, hh * hw * g_c);
+                if (c.h0 >= 0 && w1 <= W - 1) put(c.h0 * W + w1, hh * c.lw * g_c);
+                if (h1 <= H - 1 && c.w0 >= 0) put(h1 * W + c.w0, c.lh * hw * g_c);
+                if (h1 <= H - 1 && w1 <= W - 1) put(h1 * W + w1, c.lh * c.lw * g_c);
+            }
+        }
+    }
+    if (PASS == 0) det_max_commit(mx, m_gc);
+}
+
 inline int nblocks(long total) { long b = (total + 255) / 256; if (b > 16384) b = 16384; if (b < 1) b = 1; return (int)b; }
 
 }  // namespace
@@ -330,6 +559,44 @@ int ptta_launch_nl_affinity_bwd(const GView& oa, const float* conf, const float*
                                 const GView& goa, float* gconf, hipStream_t s) {
     hipLaunchKernelGGL(nl_affinity_bwd_kernel, dim3(nblocks((long)oa.B * oa.H * oa.W)), dim3(256), 0, s, oa, conf, S, legacy, goff9,
                        gaff9, goa, gconf);
+    PTTA_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- deterministic forms: workspace = PTTA_NL_DET_SLOTS maxima (uint32 bit patterns) followed by one int64 per pixel of the batch --------
+static int clog2(long v) { int n = 0; while ((1L << n) < v) ++n; return n; }
+size_t ptta_nl_det_ws_bytes(int B, int H, int W) { return PTTA_NL_DET_SLOTS * sizeof(unsigned) + (size_t)B * H * W * sizeof(unsigned long long); }
+int ptta_launch_nl_absmax(const float* x, long n, unsigned* slot, hipStream_t s) {
+    hipLaunchKernelGGL(nl_absmax_kernel, dim3(nblocks(n)), dim3(256), 0, s, x, n, slot);
+    PTTA_CHECK_LAUNCH();
+    return 0;
+}
+int ptta_launch_nl_affsum_max(const float* aff9, int B, int H, int W, unsigned* slot, hipStream_t s) {
+    hipLaunchKernelGGL(nl_affsum_max_kernel, dim3(nblocks((long)B * H * W)), dim3(256), 0, s, aff9, B, (long)H * W, slot);
+    PTTA_CHECK_LAUNCH();
+    return 0;
+}
+int ptta_launch_nl_prop_bwd_det(const float* pinned, const float* fix, const float* off9, const float* aff9, const float* gout, float* gfeat,
+                                float* goff9, float* gaff9, int B, int H, int W, unsigned long long* acc, const unsigned* m_aff,
+                                const unsigned* m_gout, unsigned* m_gfeat, hipStream_t s) {
+    const int tiles = B * ((W + PB_T - 1) / PB_T) * ((H + PB_T - 1) / PB_T);
+    const long n = (long)B * H * W;
+    const int nbits = clog2(n);
+    hipLaunchKernelGGL(nl_prop_bwd_det_kernel, dim3(tiles), dim3(256), 0, s, pinned, fix, off9, aff9, gout, acc, goff9, gaff9, B, H, W, m_aff, m_gout, nbits);
+    PTTA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nl_det_convert_kernel, dim3(nblocks(n)), dim3(256), 0, s, acc, gfeat, n, m_aff, m_gout, nbits, m_gfeat);
+    PTTA_CHECK_LAUNCH();
+    return 0;
+}
+int ptta_launch_nl_affinity_bwd_det(const GView& oa, const float* conf, const float* S, int legacy, const float* goff9, const float* gaff9,
+                                    const GView& goa, float* gconf, unsigned long long* acc, unsigned* m_gc, hipStream_t s) {
+    const long n = (long)oa.B * oa.H * oa.W;
+    const int nbits = clog2(n) + 3;                    // eight taps per pixel
+    hipLaunchKernelGGL(nl_affinity_bwd_det_kernel<0>, dim3(nblocks(n)), dim3(256), 0, s, oa, conf, S, legacy, goff9, gaff9, goa, acc, m_gc, nbits);
+    PTTA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nl_affinity_bwd_det_kernel<1>, dim3(nblocks(n)), dim3(256), 0, s, oa, conf, S, legacy, goff9, gaff9, goa, acc, m_gc, nbits);
+    PTTA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nl_det_convert_kernel, dim3(nblocks(n)), dim3(256), 0, s, acc, gconf, n, (const unsigned*)m_gc, (const unsigned*)nullptr, nbits, (unsigned*)nullptr);
     PTTA_CHECK_LAUNCH();
     return 0;
 }

@@ -506,6 +506,11 @@ int ptta_set_option(ptta_handle c, const char* key, int value) {
         if (c->nl->head_bn_fused != value) { c->nl->drop_graphs(); c->nl->head_bn_fused = value; }
         return 0;
     }
+    if (k == "deterministic") {                    // NLSPN handles that train: the propagation gradients' scatters in fixed point, no float atomics
+        if (!c->nl) return c->fail("ptta_set_option: 'deterministic' belongs to NLSPN handles (MSG_CHN's step is bit-reproducible as it is)", -38);
+        c->err.clear();
+        return c->nl->set_deterministic(value);
+    }
     if (c->nl) return -38;                         // the generic engine has no other switch
     if (k == "pair_fuse_count" || k == "tpair_fuse_count") return c->fail("ptta_set_option: '" + k + "' is read-only", -22);
     const Option* o = find_option(k);
@@ -540,6 +545,7 @@ int ptta_get_option(ptta_handle c, const char* key, int* value) {
         *value = k == "head_bn_fused" ? c->nl->head_bn_fused : c->nl->head_bn_fused_count();
         return 0;
     }
+    if (k == "deterministic") return c->nl ? c->nl->get_deterministic(value) : -38;
     if (c->nl) { if (k != "graph") return -38; *value = c->nl->use_graph; return 0; }
     if (k == "graph") { *value = c->use_graph; return 0; }
     // read-only: how many (stride-2 -> stride-1) layer pairs the last step issued as ONE launch (a replayed graph: as it was captured)

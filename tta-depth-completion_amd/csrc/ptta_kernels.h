@@ -370,6 +370,20 @@ int ptta_launch_nl_prop_bwd(const float* pinned, const float* fix, const float* 
                             float* goff9, float* gaff9, int B, int H, int W, hipStream_t s);
 int ptta_launch_nl_affinity_bwd(const GView& oa, const float* conf, const float* S, int legacy, const float* goff9, const float* gaff9,
                                 const GView& goa, float* gconf, hipStream_t s);
+// The deterministic forms of the two gradients above (option "deterministic"; nlspn_prop.hip states the arithmetic): the scatters add 64-bit
+// fixed-point integers, so no float atomic remains.  Workspace: PTTA_NL_DET_SLOTS uint32 maxima (bit patterns of |x|, zeroed by the caller
+// before the first reduction into them) and `acc`, one int64 per pixel of the batch, zero on entry and zero again on return.
+#define PTTA_NL_DET_SLOTS 64
+size_t ptta_nl_det_ws_bytes(int B, int H, int W);
+int ptta_launch_nl_absmax(const float* x, long n, unsigned* slot, hipStream_t s);                           // *slot = max(*slot, bits of max|x|)
+int ptta_launch_nl_affsum_max(const float* aff9, int B, int H, int W, unsigned* slot, hipStream_t s);      // ... of max over pixels of sum_k |aff9_k|
+// gfeat is overwritten (no memset in front); m_aff / m_gout: the two maxima above for this aff9 / gout; m_gfeat (may be null) receives max|gfeat|
+int ptta_launch_nl_prop_bwd_det(const float* pinned, const float* fix, const float* off9, const float* aff9, const float* gout, float* gfeat,
+                                float* goff9, float* gaff9, int B, int H, int W, unsigned long long* acc, const unsigned* m_aff,
+                                const unsigned* m_gout, unsigned* m_gfeat, hipStream_t s);
+// gconf is overwritten; m_gc: a zeroed slot (receives max|g_c|)
+int ptta_launch_nl_affinity_bwd_det(const GView& oa, const float* conf, const float* S, int legacy, const float* goff9, const float* gaff9,
+                                    const GView& goa, float* gconf, unsigned long long* acc, unsigned* m_gc, hipStream_t s);
 
 // ---- gconv_mfma.hip: matrix-core (bf16x3) stride-1 convolution over 1-2 NHWC sources -------------------------------
 struct GX3Args {

@@ -2,7 +2,7 @@
 // stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_gconv, ptta_op_gconv_affine, ptta_op_gbn, ptta_op_conv32_chain,
 // CostDCNet's own kernels: ptta_cd_sparse_*, ptta_op_cd_sparse_conv, ptta_op_cd_sbn, ptta_op_cd_densify, ptta_op_cd_dense, and the MSG_CHN
 // step's first-layer / prediction convolutions, resamplings and loss: ptta_op_conv_in, ptta_op_conv_out1, ptta_op_prep, ptta_op_up2_1ch,
-// ptta_op_up2t_1ch, ptta_op_up2t_32, ptta_op_loss).
+// ptta_op_up2t_1ch, ptta_op_up2t_32, ptta_op_loss; NLSPN's propagation gradients in both forms: ptta_op_nl_prop_bwd, ptta_op_nl_affinity_bwd).
 #include "msgchn_ctx.h"
 #include "gnet.h"
 #include "costdc.h"
@@ -916,6 +916,75 @@ int ptta_op_conv32_chain(const float* in, const float* weight, const float* bias
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (cs) (void)hipStreamDestroy(cs);
+    return rc;
+}
+
+// ---- NLSPN's propagation gradients, stand-alone (tests/test_gpu_nlspn_det_elementwise.py, tools/bench_nlspn_deterministic.py) ----------------
+// form 0: the float-atomic kernels of the default step; form 1: the fixed-point forms of option "deterministic", launched as the engine's
+// backward launches them.  scratch: ptta_nl_det_scratch_bytes(b, h, w) bytes, 8-byte aligned (form 1 only).
+int64_t ptta_nl_det_scratch_bytes(int b, int h, int w) { return (b < 1 || h < 1 || w < 1) ? -22 : (int64_t)ptta_nl_det_ws_bytes(b, h, w); }
+
+static bool op_nl_ok(int b, int h, int w, int form, const void* scratch) {
+    return b >= 1 && h >= 1 && w >= 1 && (double)b * h * w < 2.0e9 && form >= 0 && form <= 1 && (form == 0 || (scratch && op_al(scratch, 8)));
+}
+int ptta_op_nl_prop_bwd(const float* pinned, const float* fix, const float* off9, const float* aff9, const float* gout, float* gfeat,
+                        float* goff9, float* gaff9, int b, int h, int w, int form, void* scratch, int reps, float* us_per_call_host,
+                        ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!pinned || !fix || !off9 || !aff9 || !gout || !gfeat || !goff9 || !gaff9 || !op_nl_ok(b, h, w, form, scratch) || reps < 0 ||
+        (reps > 0 && !us_per_call_host)) return -22;
+    const long n = (long)b * h * w;
+    unsigned* mx = (unsigned*)scratch;
+    unsigned long long* acc = (unsigned long long*)((char*)scratch + PTTA_NL_DET_SLOTS * sizeof(unsigned));
+    int rc = 0;
+    if (form == 1) {            // the maxima the engine keeps per backward: of sum|aff9| and of this sweep's gout
+        if (hipMemsetAsync(scratch, 0, ptta_nl_det_ws_bytes(b, h, w), s) != hipSuccess) rc = -5;
+        if (!rc) rc = ptta_launch_nl_affsum_max(aff9, b, h, w, mx, s);
+        if (!rc) rc = ptta_launch_nl_absmax(gout, n, mx + 1, s);
+    }
+    auto run = [&]() {
+        if (form == 1) return ptta_launch_nl_prop_bwd_det(pinned, fix, off9, aff9, gout, gfeat, goff9, gaff9, b, h, w, acc, mx, mx + 1, mx + 2, s);
+        if (hipMemsetAsync(gfeat, 0, (size_t)n * sizeof(float), s) != hipSuccess) return -5;
+        return ptta_launch_nl_prop_bwd(pinned, fix, off9, aff9, gout, gfeat, goff9, gaff9, b, h, w, s);
+    };
+    if (!rc) rc = run();
+    if (!rc && reps > 0) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = -5;
+        if (!rc) {
+            (void)hipEventRecord(e0, s);
+            for (int r = 0; r < reps && !rc; ++r) rc = run();
+            (void)hipEventRecord(e1, s);
+            (void)hipEventSynchronize(e1);
+            float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1);
+            *us_per_call_host = 1e3f * ms / (float)reps;
+        }
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    if (rc > 0) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+
+int ptta_op_nl_affinity_bwd(const float* oa_nhwc, const float* conf, const float* aff_scale, int legacy, const float* goff9, const float* gaff9,
+                            float* goa_nhwc, float* gconf, int b, int h, int w, int form, void* scratch, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!oa_nhwc || !conf || !aff_scale || !goff9 || !gaff9 || !goa_nhwc || !gconf || !op_nl_ok(b, h, w, form, scratch)) return -22;
+    GView oa, goa;
+    oa.p = (float*)oa_nhwc; oa.B = b; oa.H = h; oa.W = w; oa.C = 24; oa.ld = 24;
+    goa = oa; goa.p = goa_nhwc;
+    int rc = 0;
+    if (form == 1) {
+        if (hipMemsetAsync(scratch, 0, ptta_nl_det_ws_bytes(b, h, w), s) != hipSuccess) rc = -5;
+        if (!rc) rc = ptta_launch_nl_affinity_bwd_det(oa, conf, aff_scale, legacy ? 1 : 0, goff9, gaff9, goa, gconf,
+                                                      (unsigned long long*)((char*)scratch + PTTA_NL_DET_SLOTS * sizeof(unsigned)), (unsigned*)scratch, s);
+    } else {
+        if (hipMemsetAsync(gconf, 0, (size_t)b * h * w * sizeof(float), s) != hipSuccess) rc = -5;
+        if (!rc) rc = ptta_launch_nl_affinity_bwd(oa, conf, aff_scale, legacy ? 1 : 0, goff9, gaff9, goa, gconf, s);
+    }
+    if (rc > 0) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
     return rc;
 }
 

@@ -214,6 +214,9 @@ SIGNATURES = [
     ('ptta_op_up2t_1ch', c_int, [_P, _P, c_int, c_int, c_int, _P]),
     ('ptta_op_up2t_32', c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     ('ptta_op_loss', c_int, [POINTER(LossArgs), _P]),
+    ('ptta_nl_det_scratch_bytes', c_int64, [c_int, c_int, c_int]),
+    ('ptta_op_nl_prop_bwd', c_int, [_P] * 8 + [c_int] * 4 + [_P, c_int, POINTER(c_float), _P]),
+    ('ptta_op_nl_affinity_bwd', c_int, [_P, _P, _P, c_int, _P, _P, _P, _P] + [c_int] * 4 + [_P, _P]),
     ('ptta_version', c_int, []),
 ]
 

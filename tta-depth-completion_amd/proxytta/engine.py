@@ -463,7 +463,8 @@ class Engine:
 
     def set_option(self, key, value):
         """Per-handle switch (include/ptta.h ptta_set_option: graph, aux_stream, thru, fuse_first, fuse_head_bwd, fuse_heads, heads_v2,
-        cos_in_gemm, mask_bits, stamps, pair_fuse, tpair_fuse; eval_bn_fused, head_bn_fused on the generic engine's handles)."""
+        cos_in_gemm, mask_bits, stamps, pair_fuse, tpair_fuse; eval_bn_fused, head_bn_fused on the generic engine's handles, deterministic on
+        NLSPN's)."""
         self._chk(self.lib.ptta_set_option(self.handle, key.encode(), int(value)), 'ptta_set_option(%s)' % key)
 
     def get_option(self, key):
@@ -616,6 +617,48 @@ def op_gwgrad(x_nhwc, gy_nhwc, impl='default', with_bias=True, reps=0):
     if rc != 0:
         raise RuntimeError('ptta_op_gwgrad failed (%d)' % rc)
     return gw, gb, (us.value if reps > 0 else None)
+
+
+def _nl_scratch(form, b, h, w, device):
+    """The fixed-point forms' workspace (include/ptta.h ptta_nl_det_scratch_bytes); form 0 takes none."""
+    if not form:
+        return None
+    return torch.empty(int(_lib.load().ptta_nl_det_scratch_bytes(b, h, w)) // 8, device=device, dtype=torch.int64)
+
+
+def op_nl_prop_bwd(pinned, fix, off9, aff9, gout, goff9, gaff9, form=0, reps=0):
+    """Test / measurement hook (include/ptta.h ptta_op_nl_prop_bwd): one NLSPN propagation sweep's gradient from planar fp32 maps pinned, fix,
+    gout [b, h, w], off9 [b, 18, h, w], aff9 [b, 9, h, w].  form 0: the float-atomic kernel, 1: the fixed-point form of option
+    'deterministic'.  goff9 / gaff9 are accumulated into in place.  Returns (gfeat [b, h, w], microseconds per sweep of `reps` timed sweeps)."""
+    lib = _lib.load()
+    b, h, w = gout.shape
+    assert tuple(off9.shape) == (b, 18, h, w) == tuple(goff9.shape) and tuple(aff9.shape) == (b, 9, h, w) == tuple(gaff9.shape)
+    assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (pinned, fix, off9, aff9, gout, goff9, gaff9))
+    gfeat = torch.full((b, h, w), float('nan'), device=gout.device, dtype=torch.float32)
+    scratch = _nl_scratch(form, b, h, w, gout.device)
+    us = ctypes.c_float(0.0)
+    rc = lib.ptta_op_nl_prop_bwd(ptr(pinned), ptr(fix), ptr(off9), ptr(aff9), ptr(gout), ptr(gfeat), ptr(goff9), ptr(gaff9), b, h, w, int(form),
+                                 ptr(scratch), int(reps), byref(us), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_nl_prop_bwd failed (%d)' % rc)
+    return gfeat, (us.value if reps > 0 else None)
+
+
+def op_nl_affinity_bwd(oa, conf, aff_scale, goff9, gaff9, legacy=False, form=0):
+    """Test hook (include/ptta.h ptta_op_nl_affinity_bwd): gradient of NLSPN's fused affinity pass.  oa [b, h, w, 24] contiguous NHWC, conf
+    [b, h, w], aff_scale a one-element device tensor, goff9 [b, 18, h, w], gaff9 [b, 9, h, w].  Returns (g_oa [b, h, w, 24], gconf [b, h, w])."""
+    lib = _lib.load()
+    b, h, w, c = oa.shape
+    assert c == 24 and tuple(goff9.shape) == (b, 18, h, w) and tuple(gaff9.shape) == (b, 9, h, w) and tuple(conf.shape) == (b, h, w)
+    assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (oa, conf, aff_scale, goff9, gaff9))
+    goa = torch.full((b, h, w, 24), float('nan'), device=oa.device, dtype=torch.float32)
+    gconf = torch.full((b, h, w), float('nan'), device=oa.device, dtype=torch.float32)
+    scratch = _nl_scratch(form, b, h, w, oa.device)
+    rc = lib.ptta_op_nl_affinity_bwd(ptr(oa), ptr(conf), ptr(aff_scale), int(bool(legacy)), ptr(goff9), ptr(gaff9), ptr(goa), ptr(gconf), b, h, w,
+                                     int(form), ptr(scratch), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_nl_affinity_bwd failed (%d)' % rc)
+    return goa, gconf
 
 
 GCONV_GEOMS = {'s1': 0, 's2': 1, 't2': 2}

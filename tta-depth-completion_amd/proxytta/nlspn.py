@@ -17,6 +17,8 @@ before each concatenation as in nlspnmodel_adapt.py:474-490 (NYUv2's 228 x 304 i
 The eval path's biharmonic hole filling (src/nlspn_model_adapt.py:124-127, skimage on the CPU) is `_fill` below: `fill_holes` True (the
 default) runs it on the host as the reference does, 'device' on the device (include/ptta.h ptta_inpaint_biharmonic), False returns the exact
 zeros of the clamped output as zeros.
+`deterministic` (default False): True runs the propagation gradients of every training engine without float atomics (include/ptta.h option
+'deterministic'), so that repeating a run on the same frames gives the same bits.
 """
 import torch
 
@@ -62,7 +64,21 @@ class NlspnModel_Adapt(_AdapterBase):
         self.max_depth = max_depth
         self.adapt_mode = 'meta_bn'
         self.fill_holes = True            # eval forward: biharmonic hole filling like the reference, on the host ('device': on the device; False: the raw network output)
+        self._deterministic = False
         super().__init__(max_depth, max_input_depth, device)
+
+    @property
+    def deterministic(self):
+        """True: every engine that trains runs the propagation gradients without float atomics (include/ptta.h option 'deterministic'): the
+        same frames give the same bits on every run.  Holds for the engines created from then on and for the live ones."""
+        return self._deterministic
+
+    @deterministic.setter
+    def deterministic(self, value):
+        self._deterministic = bool(value)
+        for eng in self._engines.values():
+            if eng.adapted:                       # (the source model has no backward: the library refuses the option there)
+                eng.set_option('deterministic', int(self._deterministic))
 
     @staticmethod
     def _init(name, shape):
@@ -116,8 +132,11 @@ class NlspnModel_Adapt(_AdapterBase):
 
     def _new_engine(self, n, h, w, plain_mode=None):
         """plain_mode: the engine without the meta layer (include/ptta.h PTTA_META_NONE) in that adapt mode."""
-        return Engine(n, h, w, backbone='nlspn', legacy_offset=self.legacy, max_input_depth=self.max_input_depth, syncbn_adapted=self.sync_bn,
-                      meta='none' if plain_mode else self.meta, adapt_mode=plain_mode or self.adapt_mode, **self.hparams)
+        eng = Engine(n, h, w, backbone='nlspn', legacy_offset=self.legacy, max_input_depth=self.max_input_depth, syncbn_adapted=self.sync_bn,
+                     meta='none' if plain_mode else self.meta, adapt_mode=plain_mode or self.adapt_mode, **self.hparams)
+        if self._deterministic and eng.adapted:
+            eng.set_option('deterministic', 1)
+        return eng
 
     def forward(self, image, sparse_depth, intrinsics=None, crop_mask=None, loss_type='pretrain'):
         if is_plain_loss_type(loss_type):
