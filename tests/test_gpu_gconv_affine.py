@@ -1,4 +1,4 @@
-"""The per-channel affine epilogue of the generic engine's matrix-core convolutions (csrc/gconv_mfma.hip, GX3Args::scale), through
+"""The per-channel affine epilogue of the generic engine's matrix-core convolutions (csrc/gconv_x3_s1.hip and gconv_x3_strided.hip, GX3Args::scale), through
 ptta_op_gconv_affine:   y = act(fmaf(conv + bias, scale[c], shift[c]) [+ res])
 -- what the eval forward of NLSPN's meta-only mode runs where a BatchNorm2d with constant statistics follows a convolution.
 

@@ -1,4 +1,4 @@
-"""The ELU form of the affine epilogue of the generic engine's stride-1 matrix-core convolution (csrc/gconv_mfma.hip, the ELU
+"""The ELU form of the affine epilogue of the generic engine's stride-1 matrix-core convolution (csrc/gconv_x3_s1.hip, the ELU
 instantiations of gconv_x3_s1_kernel), through ptta_op_gconv_affine with act 4:
     v = fmaf(conv + bias, scale[c], shift[c]);   y = v > 0 ? v : expm1f(v)
 -- a BatchNorm3d + ELU of CostDCNet's UNet3D evaluated from constant running statistics, behind its 1x3x3 convolution (frames x planes

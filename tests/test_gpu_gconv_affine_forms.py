@@ -1,4 +1,4 @@
-"""The residual forms and the bf16x6 images of the affine epilogue of the generic engine's matrix-core convolutions (csrc/gconv_mfma.hip,
+"""The residual forms and the bf16x6 images of the affine epilogue of the generic engine's matrix-core convolutions (csrc/gconv_x3_s1.hip and gconv_x3_strided.hip,
 GX3Args::aff_act_first / aff_res_plain / six_B with GX3Args::scale), through ptta_op_gconv_affine -- what the stage-2 head trainer runs where
 a frozen BatchNorm2d follows a convolution (option "head_bn_fused"):
     act        y = act(fmaf(conv + bias, scale[c], shift[c]))

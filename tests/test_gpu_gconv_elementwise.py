@@ -1,4 +1,4 @@
-"""The generic engine's convolution kernels (csrc/gconv_mfma.hip, csrc/gconv.hip) on their own, through ptta_op_gconv, compared PER
+"""The generic engine's convolution kernels (csrc/gconv_x3_s1.hip, csrc/gconv_x3_strided.hip, csrc/gconv.hip) on their own, through ptta_op_gconv, compared PER
 ELEMENT with torch's float64 convolution on the CPU: every launch form, at the sizes, channel counts and switches listed case by case in
 tests/gconv_cases.py.  No element is left out of a comparison.
 

@@ -1,5 +1,5 @@
 """Weight gradient of a stride-1 3x3 convolution at the wide channel pairs of the 2layers meta block on NLSPN (48 <-> 256) and
-CostDCNet (16 -> 64): the bf16x3 form (gconv_mfma.hip gwgrad_x3_kernel, WIDE) through ptta_op_gwgrad against an fp64 torch weight
+CostDCNet (16 -> 64): the bf16x3 form (gwgrad_mfma.hip gwgrad_x3_kernel, WIDE) through ptta_op_gwgrad against an fp64 torch weight
 gradient, against the fp32-MFMA form it replaces, and bitwise across runs (fixed-order reduction, no atomics)."""
 import pytest
 import torch
@@ -68,6 +68,30 @@ def test_gwgrad_wide_bitwise_across_runs(ci, co):
     a = op_gwgrad(x, gy)
     b = op_gwgrad(x, gy)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+# the narrow bf16x3 forms (gwgrad_x3_kernel without WIDE): one tile pair with one partial per block (the second with a partly empty input
+# tile), 2 x 2 pairs, 1 x 4 and 4 x 1
+NARROW = [(32, 32), (24, 32), (48, 48), (64, 64), (32, 128), (128, 32)]
+
+
+@pytest.mark.parametrize('ci,co', NARROW)
+@pytest.mark.parametrize('b,h,w', MAPS)
+def test_gwgrad_narrow_forms(ci, co, b, h, w):
+    from proxytta.engine import op_gwgrad
+    x, gy = _maps(b, h, w, ci, co, seed=ci * 1000 + co + h)
+    rw, rb = _ref(x, gy)
+    gw, gb, _ = op_gwgrad(x, gy)
+    gw2, gb2, _ = op_gwgrad(x, gy)
+    fw, fb, _ = op_gwgrad(x, gy, impl='fp32_mfma')
+    ew, eb = _err(gw, rw), _err(gb, rb)
+    print('%d -> %d %dx%dx%d: bf16x3 narrow weight %.2e bias %.2e' % (ci, co, b, h, w, ew, eb))
+    # bounds: twice the largest error of its kind over these twelve cases, measured on the build before the launcher was rewritten
+    # (profiles/gconv_split.txt: weight 5.824e-6 at 24 -> 32 1x24x40, bias 1.096e-7 at the same case)
+    assert ew < 2 * 5.824e-6 and eb < 2 * 1.096e-7
+    assert torch.equal(gw, gw2) and torch.equal(gb, gb2)
+    # the launcher takes a bf16x3 form at these shapes, not the fp32-MFMA one
+    assert not torch.equal(gw, fw)
 
 
 def test_gwgrad_naive_form_agrees():

@@ -1,4 +1,4 @@
-"""Weight-gradient A/B at the wide channel pairs of the 2layers meta block: the engine's launcher (bf16x3, gconv_mfma.hip
+"""Weight-gradient A/B at the wide channel pairs of the 2layers meta block: the engine's launcher (bf16x3, gwgrad_mfma.hip
 gwgrad_x3_kernel WIDE) against the fp32-MFMA form (gwgrad_mfma_kernel) it replaces, hipEvent-timed through ptta_op_gwgrad, the two forms
 alternating round by round in one process.  NLSPN 352x1216 (48 -> 256, 256 -> 48), CostDCNet 480x640 (16 -> 64), and NLSPN's 1layer
 48 -> 48 (already bf16x3) as the precedent.

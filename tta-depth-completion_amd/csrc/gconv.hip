@@ -10,7 +10,7 @@
 //   conv s2      -> transposed conv with the same weight tensor
 //   convT s2     -> conv s2 with the same weight tensor
 // Kernels here: the reference-grade direct form (exact fp32 FMA, one thread per output element), used for the small
-// layers and as the on-device check of the matrix-core path (gconv_mfma.hip).
+// layers and as the on-device check of the matrix-core path (gconv_mfma.hip and its kernel files).
 #include "ptta_common.h"
 #include "ptta_kernels.h"
 

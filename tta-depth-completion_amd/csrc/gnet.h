@@ -3,7 +3,7 @@
 //
 // A network is a flat op list built once per handle ("program"):
 //   CONV  one or two channel-concatenated NHWC sources (torch.cat never materialises), 3x3 / 1x1, stride 1 / 2 or stride-2
-//         transposed, optional fused activation; matrix-core (bf16x3) kernels of gconv_mfma.hip, direct fp32 kernels of
+//         transposed, optional fused activation; matrix-core (bf16x3) kernels of gconv_x3_s1.hip and gconv_x3_strided.hip, direct fp32 kernels of
 //         gconv.hip for odd channel counts and for PTTA_CONV_IMPL=naive validation;
 //   BN    batch-statistics normalisation (+activation, + residual add), adapted or frozen affine parameters, optionally
 //         TRACKED (running statistics updated in train mode, used in eval mode: BatchNorm3d / BatchNorm1d of CostDCNet);

@@ -218,7 +218,7 @@ int backbone_backward(ptta_ctx* c, const float* g_net, hipStream_t s, bool join_
     if (c->nar_bwd && c->meta_mode == PTTA_META_2LAYERS) RUN(to_wide(c, c->dm_total, c->dm_f32, (long)Nn * H4 * W4 * 32, s));
     if (c->meta_mode == PTTA_META_2LAYERS) return meta2_backward(c, s);
     if (!c->bf16 && c->x3 && !c->naive) {
-        // default arithmetic: the bf16x3 reduction-GEMM form (gconv_mfma.hip gwgrad_x3_kernel, single-pair mode)
+        // default arithmetic: the bf16x3 reduction-GEMM form (gwgrad_mfma.hip gwgrad_x3_kernel, single-pair mode)
         GView xv; xv.p = (float*)c->c2; xv.B = Nn; xv.H = H4; xv.W = W4; xv.C = 32; xv.ld = 32;
         GView gv; gv.p = (float*)c->dm_total; gv.B = Nn; gv.H = H4; gv.W = W4; gv.C = 32; gv.ld = 32;
         GwAdam ga;

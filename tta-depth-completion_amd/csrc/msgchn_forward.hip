@@ -252,7 +252,7 @@ static int meta_forward(ptta_ctx* c, bool train, int B, hipStream_t s) {
     const long P = (long)Nn * H4 * W4;                         // pixels per pass
     const int npass = train ? B / Nn : 1;
     if (m2.generic) {
-        // one matrix-core launch per convolution on NHWC-128 tensors (gconv_mfma.hip), BatchNorm statistics reduced in the
+        // one matrix-core launch per convolution on NHWC-128 tensors (gconv_x3_s1.hip), BatchNorm statistics reduced in the
         // conv epilogues, one finalize per pass (running statistics: real frames first, then proxy frames), one apply
         if (!train && (!m2.rm1 || !m2.rv1 || !m2.rm2 || !m2.rv2)) return c->fail("meta BatchNorm running statistics not loaded", -3);
         GView x; x.p = (float*)c->c2; x.B = B; x.H = H4; x.W = W4; x.C = 32; x.ld = 32;

@@ -385,7 +385,7 @@ int ptta_launch_nl_prop_bwd_det(const float* pinned, const float* fix, const flo
 int ptta_launch_nl_affinity_bwd_det(const GView& oa, const float* conf, const float* S, int legacy, const float* goff9, const float* gaff9,
                                     const GView& goa, float* gconf, unsigned long long* acc, unsigned* m_gc, hipStream_t s);
 
-// ---- gconv_mfma.hip: matrix-core (bf16x3) stride-1 convolution over 1-2 NHWC sources -------------------------------
+// ---- gconv_mfma.hip and its kernel files (gconv_x3_s1.hip, gconv_x3_strided.hip, gwgrad_mfma.hip): matrix-core (bf16x3) stride-1 convolution over 1-2 NHWC sources -------------------------------
 struct GX3Args {
     const float* x0 = nullptr; int C0 = 0, ld0 = 0;
     const float* x1 = nullptr; int C1 = 0, ld1 = 0;
@@ -438,7 +438,7 @@ int ptta_launch_gconv_x3_strided(const GX3Args& a, int ks, int mode, int hin, in
 enum { GX3_FORM_PLAIN = 0, GX3_FORM_NCO2 = 1, GX3_FORM_KSPLIT = 2 };
 int ptta_gconv_x3_strided_form(const GX3Args& a, int ks, int mode, int win, long* nitems_out = nullptr);
 long ptta_gwgrad_mfma_part_floats(long pixels, int Ci, int Co);
-// Adam applied by the weight gradient's reduction itself (gconv_mfma.hip gwgrad_mfma_reduce_kernel; <= 32 x 32 channels, the single-pair bf16x3 form only;
+// Adam applied by the weight gradient's reduction itself (gwgrad_mfma.hip gwgrad_mfma_reduce_kernel; <= 32 x 32 channels, the single-pair bf16x3 form only;
 // ptta_launch_gwgrad_mfma returns -22 for any other shape with ad.pw set): parameter + both
 // moments of the weight and of the bias, the hyper-parameter block, the device step count and its ticket (as ptta_launch_adam_multi)
 struct GwAdam { float *pw = nullptr, *mw = nullptr, *vw = nullptr, *pb = nullptr, *mb = nullptr, *vb = nullptr; const float* hyper = nullptr; int* step = nullptr; unsigned* ticket = nullptr; };
