@@ -1046,6 +1046,49 @@ int ptta_op_nl_prop_bwd(const float* pinned, const float* fix, const float* off9
                         ptta_stream s);
 int ptta_op_nl_affinity_bwd(const float* oa_nhwc, const float* conf, const float* aff_scale, int legacy, const float* goff9, const float* gaff9,
                             float* goa_nhwc, float* gconf, int b, int h, int w, int form, void* scratch, ptta_stream s);
+/* Test hooks: the narrow heads of the mixed mode (csrc/heads_n.hip) and head_bwd_finish (csrc/heads_bn.hip) stand-alone, launched through
+ * the launchers of csrc/ptta_kernels.h (tests/test_gpu_heads_n_elementwise.py).  All of them synchronise; -12 out of memory, -5 a HIP error.
+ *
+ * Layouts.  A narrow [R][512] activation is TILED: T[r / 128][k / 32][r % 128][k % 32] bf16, ptta_op_hn_tiled_elems(R) = ceil(R / 128) * 128 *
+ * 512 elements -- the rows from R on of the last block are padding: the GEMM reads them (their results land in the output's padding) and no
+ * result of a row below R depends on them.  part [ceil(R / 128)][2][512] fp32: per 128-row block the column sums (epi 1: sum v | sum v^2
+ * of the fp32 values; epi 3: sum g | sum g xhat of the masked gradient), rows below R only.  rs [R]: row sums of squares of the STORED
+ * values.  rowstats / rowstats_out [R][3] = (|e|, |c|, cos), both norms floored at 1e-12.  cpart [cpart_n]: slot b < ceil(R / 128) = block
+ * b's sum of 2 - 2 cos over its rows below R, the slots from ceil(R / 128) on are cleared.  P [R][32] fp32.
+ *
+ * ptta_op_hn_gemm: one field per field of HnGemmArgs, passed through to the launcher ptta_launch_hn_gemm; -22 exactly where that returns -22: W NULL,
+ * r < 1, a pointer its pro / epi needs NULL, cpart_n below the grid, a key other than 10 11 12 30 31 35 43 53.  A, Bref, E, C: device buffers
+ * in the tiled layout.  W [512][512], W0 [512][32], W0t [32][512] arrive as fp32 row-major and are converted inside the call the way
+ * csrc/msgchn_build.hip converts them: ptta_split_weight's hi plane, then ptta_hn_pack_w for W; w_image (may be NULL) receives the packed
+ * slice-major image of W, [16][512][32] bf16 with 16-byte chunk c of row n at c ^ ((n >> 2) & 3).  Scratch is allocated and freed inside.
+ * ptta_op_hn_moments: ptta_launch_hn_moments on X [npass][r][32] (fp32, or bf16 with x_bf16), W0 [512][32] and b0 fp32 -> part [npass][2][2][512]
+ * (sum h | sum h^2 as a float value and the remainder its rounding lost), or with bn != 0 the BatchNorm1d state directly: gamma, beta in;
+ * mean, inv, scale, shift [512] out; rm, rv (both or neither), nbt optional.  -22 where the launcher returns it (a NULL input, r < 1,
+ * npass < 1, bn with npass != 1) and for bn with gamma, beta, mean, inv, scale or shift NULL or rm without rv (the kernel would dereference them).
+ * ptta_op_hn_untile: tiled bf16 -> dst [r][512] fp32.  ptta_op_head_bwd_finish: dX [r][32] (fp32, or bf16 with dx_bf16) = P - X M - u with
+ * M, u from k12 [2][512] doubles and W0 [512][32] fp32 (csrc/heads_bn.hip); P [halves][r][32], halves 1 or 2 (else -22). */
+long long ptta_op_hn_tiled_elems(long long r);      /* elements of a tiled [r][512] buffer; -22 for r < 1 */
+typedef struct ptta_hn_gemm_args {
+    int pro, epi, x_bf16, cpart_n;
+    long long r;
+    const void* A; const float* Af; const void* Bref; const float* rowstats; const float* coef; const void* X;
+    const float* W0; const float* b0; const float* pscale; const float* pshift; const float* W; const float* bias;
+    void* C; float* part; const void* E; float* rs; float* rowstats_out; float* cpart;
+    const float* escale; const float* eshift; const float* emean; const float* einv; const float* W0t; float* P;
+    void* w_image;
+} ptta_hn_gemm_args;
+int ptta_op_hn_gemm(const ptta_hn_gemm_args* a, ptta_stream s);
+typedef struct ptta_hn_moments_args {
+    int x_bf16, npass, bn;
+    long long r;
+    float eps, momentum;
+    const void* X; const float* W0; const float* b0; float* part;
+    const float* gamma; const float* beta; float* rm; float* rv; long long* nbt; float* mean; float* inv; float* scale; float* shift;
+} ptta_hn_moments_args;
+int ptta_op_hn_moments(const ptta_hn_moments_args* a, ptta_stream s);
+int ptta_op_hn_untile(const void* src_tiled, float* dst, long long r, ptta_stream s);
+int ptta_op_head_bwd_finish(const double* k12, const float* W0, const float* P, const float* X, long long r, void* dX, int halves, int dx_bf16,
+                            ptta_stream s);
 /* Diagnostic (tools/bench_chain.py): `reps` dependent launches of one stride-1 32->32 convolution (fp32 NHWC, default arithmetic) captured
  * into one hipGraph and replayed `replays` times: microseconds per launch INSIDE a replayed graph.  epi_flags: 2 = ReLU mask from `aux`,
  * 4 = skip addition of `aux`, 8 = the same chain launched directly (no graph), 16 = the layer loop (ONE launch per `reps` layers with a

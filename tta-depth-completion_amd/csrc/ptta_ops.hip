@@ -2,7 +2,8 @@
 // stand-alone operator launches tests and tools/ time (ptta_op_conv32, ptta_op_gwgrad, ptta_op_gconv, ptta_op_gconv_affine, ptta_op_gbn, ptta_op_conv32_chain,
 // CostDCNet's own kernels: ptta_cd_sparse_*, ptta_op_cd_sparse_conv, ptta_op_cd_sbn, ptta_op_cd_densify, ptta_op_cd_dense, and the MSG_CHN
 // step's first-layer / prediction convolutions, resamplings and loss: ptta_op_conv_in, ptta_op_conv_out1, ptta_op_prep, ptta_op_up2_1ch,
-// ptta_op_up2t_1ch, ptta_op_up2t_32, ptta_op_loss; NLSPN's propagation gradients in both forms: ptta_op_nl_prop_bwd, ptta_op_nl_affinity_bwd).
+// ptta_op_up2t_1ch, ptta_op_up2t_32, ptta_op_loss; NLSPN's propagation gradients in both forms: ptta_op_nl_prop_bwd, ptta_op_nl_affinity_bwd;
+// the mixed mode's narrow heads: ptta_op_hn_gemm, ptta_op_hn_moments, ptta_op_hn_untile, ptta_op_head_bwd_finish).
 #include "msgchn_ctx.h"
 #include "gnet.h"
 #include "costdc.h"
@@ -983,6 +984,82 @@ int ptta_op_nl_affinity_bwd(const float* oa_nhwc, const float* conf, const float
         if (hipMemsetAsync(gconf, 0, (size_t)b * h * w * sizeof(float), s) != hipSuccess) rc = -5;
         if (!rc) rc = ptta_launch_nl_affinity_bwd(oa, conf, aff_scale, legacy ? 1 : 0, goff9, gaff9, goa, gconf, s);
     }
+    if (rc > 0) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+
+// ---- the narrow heads of the mixed mode and head_bwd_finish, stand-alone (tests/test_gpu_heads_n_elementwise.py) --------------------------
+// Thin: convert the fp32 weights the way msgchn_build.hip does, launch, synchronise, return the launcher's code.  include/ptta.h states the
+// arguments and layouts.
+long long ptta_op_hn_tiled_elems(long long r) { return r < 1 ? -22 : (long long)ptta_hn_tiled_elems((long)r); }
+
+// the hi plane of ptta_split_weight for an fp32 [n] weight (NULL stays NULL); `lo` is the split's other output, shared scratch of n elements
+static const bf16_t* op_hn_hi(OpBufs& m, const float* w, long n, bf16_t* lo, hipStream_t s) {
+    if (!w) return nullptr;
+    bf16_t* hi = (bf16_t*)m.get((size_t)n * 2);
+    if (hi && lo) ptta_split_weight(w, hi, lo, nullptr, n, 512, s);
+    return hi;
+}
+
+int ptta_op_hn_gemm(const ptta_hn_gemm_args* a, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!a) return -22;
+    OpBufs m;
+    HnGemmArgs g;
+    g.pro = a->pro; g.epi = a->epi; g.x_bf16 = a->x_bf16; g.cpart_n = a->cpart_n; g.R = (long)a->r;
+    g.A = (const bf16_t*)a->A; g.Af = a->Af; g.Bref = (const bf16_t*)a->Bref; g.rowstats = a->rowstats; g.coef = a->coef; g.X = a->X;
+    g.b0 = a->b0; g.pscale = a->pscale; g.pshift = a->pshift; g.bias = a->bias;
+    g.C = (bf16_t*)a->C; g.part = a->part; g.E = (const bf16_t*)a->E; g.rs = a->rs; g.rowstats_out = a->rowstats_out; g.cpart = a->cpart;
+    g.escale = a->escale; g.eshift = a->eshift; g.emean = a->emean; g.einv = a->einv; g.P = a->P;
+    bf16_t* lo = (bf16_t*)m.get((size_t)512 * 512 * 2);
+    const bf16_t* whi = op_hn_hi(m, a->W, 512L * 512, lo, s);
+    g.W0 = op_hn_hi(m, a->W0, 512L * 32, lo, s);
+    g.W0t = op_hn_hi(m, a->W0t, 32L * 512, lo, s);
+    bf16_t* wsl = a->W ? (bf16_t*)m.get((size_t)512 * 512 * 2) : nullptr;
+    if (!m.ok) return -12;
+    if (wsl) ptta_hn_pack_w(whi, wsl, 512, s);
+    g.W = wsl;
+    int rc = ptta_launch_hn_gemm(g, s);
+    if (rc > 0) rc = -5;
+    if (!rc && a->w_image && hipMemcpyAsync(a->w_image, wsl, (size_t)512 * 512 * 2, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+
+int ptta_op_hn_moments(const ptta_hn_moments_args* a, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!a) return -22;
+    if (a->bn && (!a->gamma || !a->beta || !a->mean || !a->inv || !a->scale || !a->shift || (a->rm != nullptr) != (a->rv != nullptr))) return -22;
+    OpBufs m;
+    double* scratch = nullptr;
+    if (a->r >= 1 && a->npass >= 1 && (double)a->r * a->npass < 2.0e9) {
+        scratch = (double*)m.get((size_t)a->npass * (size_t)ptta_hn_moment_scratch((long)a->r) * sizeof(double));
+        if (!m.ok) return -12;
+    }
+    HnBnOut bo;
+    bo.gamma = a->gamma; bo.beta = a->beta; bo.eps = a->eps; bo.momentum = a->momentum; bo.rm = a->rm; bo.rv = a->rv; bo.nbt = a->nbt;
+    bo.mean = a->mean; bo.inv = a->inv; bo.scale = a->scale; bo.shift = a->shift;
+    int rc = ptta_launch_hn_moments(a->X, a->x_bf16, (long)a->r, a->npass, a->W0, a->b0, scratch, a->part, a->bn ? &bo : nullptr, s);
+    if (rc > 0) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+
+int ptta_op_hn_untile(const void* src_tiled, float* dst, long long r, ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!src_tiled || !dst || r < 1 || (double)r * 512 > 2.0e9) return -22;
+    int rc = ptta_launch_hn_untile(src_tiled, dst, (long)r, s);
+    if (rc > 0) rc = -5;
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
+    return rc;
+}
+
+int ptta_op_head_bwd_finish(const double* k12, const float* W0, const float* P, const float* X, long long r, void* dX, int halves, int dx_bf16,
+                            ptta_stream s_) {
+    hipStream_t s = (hipStream_t)s_;
+    if (!k12 || !W0 || !P || !X || !dX || r < 1 || (double)r * 32 > 2.0e9 || (halves != 1 && halves != 2)) return -22;
+    int rc = ptta_launch_head_bwd_finish(k12, W0, P, X, (long)r, dX, s, halves, dx_bf16 ? 1 : 0);
     if (rc > 0) rc = -5;
     if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = -5;
     return rc;

@@ -82,6 +82,17 @@ class LossArgs(ctypes.Structure):              # include/ptta.h ptta_loss_args
                 [(n, c_void_p) for n in ('depth', 'image', 'sparse', 'validity', 'emb', 'ref', 'loss_info', 'rowstats', 'gdepth', 'gref', 'coef')])
 
 
+class HnGemmArgs(ctypes.Structure):            # include/ptta.h ptta_hn_gemm_args
+    _fields_ = ([(n, c_int) for n in ('pro', 'epi', 'x_bf16', 'cpart_n')] + [('r', ctypes.c_longlong)] +
+                [(n, c_void_p) for n in ('A', 'Af', 'Bref', 'rowstats', 'coef', 'X', 'W0', 'b0', 'pscale', 'pshift', 'W', 'bias', 'C', 'part', 'E', 'rs',
+                                         'rowstats_out', 'cpart', 'escale', 'eshift', 'emean', 'einv', 'W0t', 'P', 'w_image')])
+
+
+class HnMomentsArgs(ctypes.Structure):         # include/ptta.h ptta_hn_moments_args
+    _fields_ = ([(n, c_int) for n in ('x_bf16', 'npass', 'bn')] + [('r', ctypes.c_longlong), ('eps', c_float), ('momentum', c_float)] +
+                [(n, c_void_p) for n in ('X', 'W0', 'b0', 'part', 'gamma', 'beta', 'rm', 'rv', 'nbt', 'mean', 'inv', 'scale', 'shift')])
+
+
 class SummaryArgs(ctypes.Structure):           # include/ptta.h ptta_summary_args
     _fields_ = ([(n, c_int) for n in ('n_show', 'height', 'width', 'n_images', 'rows', 'normalize', 'out_dtype')] + [('max_predict_depth', c_float)] +
                 [('rev_mean', c_float * 3), ('rev_std', c_float * 3), ('image', c_void_p * 8), ('image_div255', c_void_p * 8)] +
@@ -217,6 +228,11 @@ SIGNATURES = [
     ('ptta_nl_det_scratch_bytes', c_int64, [c_int, c_int, c_int]),
     ('ptta_op_nl_prop_bwd', c_int, [_P] * 8 + [c_int] * 4 + [_P, c_int, POINTER(c_float), _P]),
     ('ptta_op_nl_affinity_bwd', c_int, [_P, _P, _P, c_int, _P, _P, _P, _P] + [c_int] * 4 + [_P, _P]),
+    ('ptta_op_hn_tiled_elems', ctypes.c_longlong, [ctypes.c_longlong]),
+    ('ptta_op_hn_gemm', c_int, [POINTER(HnGemmArgs), _P]),
+    ('ptta_op_hn_moments', c_int, [POINTER(HnMomentsArgs), _P]),
+    ('ptta_op_hn_untile', c_int, [_P, _P, ctypes.c_longlong, _P]),
+    ('ptta_op_head_bwd_finish', c_int, [_P, _P, _P, _P, ctypes.c_longlong, _P, c_int, c_int, _P]),
     ('ptta_version', c_int, []),
 ]
 
@@ -261,5 +277,5 @@ def ptr(t):
     return c_void_p(t.data_ptr())
 
 
-__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs', 'SummaryArgs', 'ScoreArgs',
+__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs', 'HnGemmArgs', 'HnMomentsArgs', 'SummaryArgs', 'ScoreArgs',
            'LOSS_FWD', 'LOSS_BWD', 'CONV_IN_FORMS', 'SIGNATURES', 'LIB_PATH', 'byref']

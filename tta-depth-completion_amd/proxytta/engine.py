@@ -780,6 +780,64 @@ def op_gbn(mode, x, y, st, gamma, beta=None, res=None, g=None, gx=None, gres=Non
         raise RuntimeError('ptta_op_gbn failed (%d)' % rc)
 
 
+def hn_tiled_elems(r):
+    """Elements of a tiled narrow [r, 512] buffer (include/ptta.h): whole 128-row blocks."""
+    n = _lib.load().ptta_op_hn_tiled_elems(int(r))
+    if n < 0:
+        raise RuntimeError('ptta_op_hn_tiled_elems failed (%d)' % n)
+    return int(n)
+
+
+def _hn_fields(a, tensors):
+    for name, t in tensors.items():
+        if t is not None:
+            assert t.is_contiguous() and t.is_cuda, name
+            setattr(a, name, t.data_ptr())
+
+
+def op_hn_gemm(pro, epi, r, x_bf16=False, cpart_n=0, **tensors):
+    """Test hook: one GEMM of the mixed mode's narrow heads (include/ptta.h ptta_op_hn_gemm; csrc/heads_n.hip hn_gemm_kernel<pro, epi>) on
+    r rows.  `tensors`: the fields of ptta_hn_gemm_args by name -- A, Bref, E, C int16 device tensors of hn_tiled_elems(r) bf16 bit patterns in
+    the tiled layout; W [512, 512], W0 [512, 32], W0t [32, 512] fp32 row-major (converted inside the call); X [r, 32] fp32, or int16 bit
+    patterns with x_bf16; the tables and the outputs part, rs, rowstats_out, cpart, P fp32; w_image int16 [16, 512, 32] receives the packed
+    image of W.  Outputs are written in place; raises RuntimeError naming the return code otherwise."""
+    a = _lib.HnGemmArgs()
+    a.pro, a.epi, a.x_bf16, a.cpart_n, a.r = int(pro), int(epi), int(bool(x_bf16)), int(cpart_n), int(r)
+    _hn_fields(a, tensors)
+    rc = _lib.load().ptta_op_hn_gemm(byref(a), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_hn_gemm failed (%d)' % rc)
+
+
+def op_hn_moments(x, w0, b0, r, npass=1, x_bf16=False, part=None, bn=False, eps=1e-5, momentum=0.1, **state):
+    """Test hook: the moments chain of the narrow heads (include/ptta.h ptta_op_hn_moments; hn_moments_kernel -> hn_moment_reduce_kernel ->
+    hn_moment_stats_kernel): the train-mode BatchNorm1d statistics of h = x w0^T + b0 without computing h.  x [npass, r, 32] fp32, or int16
+    bf16 bit patterns with x_bf16; part [npass, 2, 2, 512] is written, or with bn the state given in `state` by the names of
+    ptta_hn_moments_args: gamma, beta in; mean, inv, scale, shift out; rm, rv, nbt (int64) updated.  Raises RuntimeError naming the return code."""
+    a = _lib.HnMomentsArgs()
+    a.x_bf16, a.npass, a.bn, a.r, a.eps, a.momentum = int(bool(x_bf16)), int(npass), int(bool(bn)), int(r), float(eps), float(momentum)
+    _hn_fields(a, dict(state, X=x, W0=w0, b0=b0, part=part))
+    rc = _lib.load().ptta_op_hn_moments(byref(a), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_hn_moments failed (%d)' % rc)
+
+
+def op_hn_untile(src_tiled, dst, r):
+    """Test hook (include/ptta.h ptta_op_hn_untile; hn_untile_kernel): a tiled narrow tensor (int16 bit patterns) -> dst [r, 512] fp32, in place."""
+    rc = _lib.load().ptta_op_hn_untile(ptr(src_tiled), ptr(dst), int(r), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_hn_untile failed (%d)' % rc)
+
+
+def op_head_bwd_finish(k12, w0, p, x, r, dx, halves=1, dx_bf16=False):
+    """Test hook (include/ptta.h ptta_op_head_bwd_finish; csrc/heads_bn.hip head_bwd_finish_kernel): dx [r, 32] (fp32, or int16 bf16 bit
+    patterns with dx_bf16) = P - x M - u from k12 [2, 512] float64, w0 [512, 32], p [halves, r, 32] and x [r, 32] fp32; written in place."""
+    assert k12.dtype == torch.float64
+    rc = _lib.load().ptta_op_head_bwd_finish(ptr(k12), ptr(w0), ptr(p), ptr(x), int(r), ptr(dx), int(halves), int(bool(dx_bf16)), _stream())
+    if rc != 0:
+        raise RuntimeError('ptta_op_head_bwd_finish failed (%d)' % rc)
+
+
 class CdSparseSet:
     """Test hook: the sparse voxel sets of CostDCNet's 3-D encoder (include/ptta.h ptta_cd_sparse) for n frames of h x w pixels, and the
     sparse kernels that run on them.  Feature tensors are fp32 device tensors [voxels of the level][channels], contiguous."""
