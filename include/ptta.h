@@ -616,6 +616,58 @@ int ptta_resize_pad(const float* src, float* dst, int n, int channels, int heigh
                     const int32_t* resize_height, const int32_t* resize_width, const int32_t* pad_top, const int32_t* pad_left,
                     int bilinear, int padding_mode, float fill, ptta_stream s);
 
+/* The augmented inner loop's frame set through ONE draw in one launch (src/tta_main.py:595-604: the geometric transform of [image, sparse
+ * depth, validity map, ground truth], then the photometric transform of the transformed image), for the draws the adapt scripts enable:
+ * crop to shape, horizontal / vertical flip, rotation, resize-and-crop, brightness / contrast / gamma / hue / saturation.
+ *   geometry   the staged chain ptta_crop_flip -> ptta_rotate -> ptta_resize_crop composed backwards from the output pixel; per sample a
+ *              stage whose flag is 0 is the identity.  The three one-channel maps are sampled nearest (each stage gathers one pixel or
+ *              a zero), the image nearest or bilinear (image_bilinear): resize's 4 taps, each a rotated pixel of 4 taps of the cropped /
+ *              flipped source, in the staged kernels' operation order and rounding: every output equals the staged calls' bit for bit.
+ *              scale_depth = resize_scaling_depth: every map, the validity map included, is divided by resize_width / crop_width.
+ *   outputs    loss_image n x 3 x crop_height x crop_width and the maps' outputs n x 1 x crop_height x crop_width.  A NULL map is skipped
+ *              together with its output (both NULL or neither).  image1 (optional): loss_image through ptta_photometric_full's uint8
+ *              path, i.e. truncated to 0..255, then brightness in the same launch, then contrast / gamma / hue / saturation by a second
+ *              launch iff `pass2` (the caller sets it when any sample's flag of those four is set; unset, the second launch is skipped
+ *              and flags of those four are ignored).  With image1 NULL the photometric fields are not read.
+ *   draws      n records in device memory, one per sample (52 bytes, no padding).  Per-sample values as ptta_crop_flip / ptta_rotate /
+ *              ptta_resize_crop / ptta_photometric_full take them: crop start (clamped into the frame), angle in degrees as fp32,
+ *              resize_height / resize_width / resize_y / resize_x, the five factors.
+ *   scratch    ptta_augment_scratch_bytes(n, crop_height, crop_width) bytes, 8-byte aligned, needed with image1 only: the 256 * n doubles
+ *              of partial grey sums the second launch reads, the per-block sums they are added from (the grid is one thread per output
+ *              pixel, whatever the frame's size; the sums are of integers, exact in any order), the second launch's per-sample tables
+ *              and one arrival counter per sample.  Zero it once before its first use; every call leaves the counters zero.
+ * One thread per output pixel writes that pixel of every output; no thread forms an address outside its sample whatever the records hold
+ * (every gather index is clamped into the cropped window).  Handle-free, enqueue only, one scratch per stream at a time.
+ * -22 before any launch, with the reason in ptta_last_error(NULL): a NULL args, image, loss_image or draws pointer; a map without its
+ * output or an output without its map; buffers that overlap; n outside 1..65535; a size < 1 or a frame of 2^31 values or more; a crop
+ * larger than the frame; image1 without a scratch of that size and alignment. */
+enum { PTTA_AUG_HFLIP = 1, PTTA_AUG_VFLIP = 2, PTTA_AUG_ROTATE = 4, PTTA_AUG_RESIZE = 8, PTTA_AUG_BRIGHTNESS = 16, PTTA_AUG_CONTRAST = 32,
+       PTTA_AUG_GAMMA = 64, PTTA_AUG_HUE = 128, PTTA_AUG_SATURATION = 256 };
+typedef struct ptta_augment_draw {
+    uint32_t flags;                       /* PTTA_AUG_*: this sample's coins */
+    int32_t crop_y, crop_x;               /* crop start (0, 0 with crop_height == height, crop_width == width: no crop) */
+    float angle_deg;
+    int32_t resize_height, resize_width, resize_y, resize_x;
+    float brightness, contrast, gamma, hue, saturation;
+} ptta_augment_draw;
+typedef struct ptta_augment_args {
+    const float* image;                   /* n x 3 x height x width fp32, contiguous */
+    const float* sparse_depth;            /* n x 1 x height x width, or NULL */
+    const float* validity_map;            /* likewise */
+    const float* ground_truth;            /* likewise */
+    float* loss_image;                    /* n x 3 x crop_height x crop_width */
+    float* sparse_depth_out;              /* n x 1 x crop_height x crop_width; NULL iff its input is */
+    float* validity_map_out;
+    float* ground_truth_out;
+    float* image1;                        /* n x 3 x crop_height x crop_width, or NULL */
+    const ptta_augment_draw* draws;       /* n records, device memory */
+    int n, height, width, crop_height, crop_width;
+    int image_bilinear, scale_depth, pass2;
+    void* scratch; int64_t scratch_bytes;
+} ptta_augment_args;
+int64_t ptta_augment_scratch_bytes(int n, int crop_height, int crop_width);
+int ptta_augment_frames(const ptta_augment_args* a, ptta_stream s);
+
 /* ptta_step enqueues its kernels directly; with ptta_set_option(h, "graph", 1) it replays a captured hipGraph of the whole step.  Graphs are re-captured after any re-binding. */
 /* model.convert_syncbn() (src/tta_main.py:326 -> SyncBatchNorm.convert_sync_batchnorm, src/msg_chn_model_adapt.py:547-556)
  * for the one-process-per-GPU run with shared adapted parameters: every training-mode BatchNorm then normalises with

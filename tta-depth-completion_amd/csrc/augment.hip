@@ -300,6 +300,12 @@ __global__ void gamma_float_kernel(const float* __restrict__ src, float* __restr
         dst[(long)b * per + i] = on ? aug_clamp01(powf(x, g)) : x;
     }
 }
+// the launch rule of pass 2, written once: ptta_photometric_full below and the fused frame-set kernel's second launch (augment_fused.hip)
+int ptta_launch_photo_pass2_full(float* img, int n, int H, int W, const double* part, const unsigned char* do_c, const float* f_c, const unsigned char* do_g,
+                                 const float* f_g, const unsigned char* do_h, const float* f_h, const unsigned char* do_s, const float* f_s, hipStream_t s) {
+    hipLaunchKernelGGL(photo_pass2_full_kernel, dim3(PH_BLOCKS, n), dim3(256), 0, s, img, H, W, part, do_c, f_c, do_g, f_g, do_h, f_h, do_s, f_s);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
 extern "C" int ptta_photometric_full(const float* src, float* dst, int n, int height, int width, const uint8_t* do_brightness, const float* f_brightness,
                                      const uint8_t* do_contrast, const float* f_contrast, const uint8_t* do_gamma, const float* f_gamma,
                                      const uint8_t* do_hue, const float* f_hue, const uint8_t* do_saturation, const float* f_saturation,
@@ -317,8 +323,8 @@ extern "C" int ptta_photometric_full(const float* src, float* dst, int n, int he
     if (!scratch) return -22;
     hipLaunchKernelGGL(photo_pass1_kernel, dim3(PH_BLOCKS, n), dim3(256), 0, (hipStream_t)stream, src, dst, height, width, do_brightness, f_brightness, scratch);
     if (do_contrast || do_gamma || do_hue || do_saturation)
-        hipLaunchKernelGGL(photo_pass2_full_kernel, dim3(PH_BLOCKS, n), dim3(256), 0, (hipStream_t)stream, dst, height, width, scratch, do_contrast, f_contrast,
-                           do_gamma, f_gamma, do_hue, f_hue, do_saturation, f_saturation);
+        return ptta_launch_photo_pass2_full(dst, n, height, width, scratch, do_contrast, f_contrast, do_gamma, f_gamma, do_hue, f_hue, do_saturation, f_saturation,
+                                            (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

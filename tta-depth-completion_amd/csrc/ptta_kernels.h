@@ -249,6 +249,11 @@ int ptta_launch_loss_valid_count(const float* sparse, const float* validity, int
 int ptta_launch_eval_metrics(const float* depth, const float* gt, long n, float min_eval, float max_eval, double* scratch, float* out4,
                              hipStream_t s);
 
+// ---- augment.hip: the second photometric pass (contrast -> gamma -> hue -> saturation on the uint8-valued image pass 1 left in `img`; part: the 256
+// partial grey sums per sample; a NULL do_* = option not configured) -- also the second launch of augment_fused.hip's frame-set kernel ----
+int ptta_launch_photo_pass2_full(float* img, int n, int H, int W, const double* part, const unsigned char* do_c, const float* f_c, const unsigned char* do_g,
+                                 const float* f_g, const unsigned char* do_h, const float* f_h, const unsigned char* do_s, const float* f_s, hipStream_t s);
+
 // ---- ptta_api.hip: a handle-free entry point's refusal -----------------------------------------
 // records `why` as what ptta_last_error(NULL) returns on the calling thread, and returns -22
 int ptta_refuse_args(const char* why);

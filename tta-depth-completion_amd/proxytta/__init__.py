@@ -6,13 +6,16 @@ GPU; constructing a model or an Engine does, and raises if the library or the de
 """
 from . import synth  # noqa: F401
 
-__all__ = ['synth', 'ExternalModel_Adapt', 'ExternalModelAdapt', 'MsgChnModel_Adapt', 'Engine']
+__all__ = ['synth', 'ExternalModel_Adapt', 'ExternalModelAdapt', 'MsgChnModel_Adapt', 'Engine', 'StepAugmenter']
 
 
 def __getattr__(name):
     if name in ('ExternalModel_Adapt', 'ExternalModelAdapt', 'MsgChnModel_Adapt', 'CANONICAL_LOSS_TYPE'):
         from . import model
         return getattr(model, name)
+    if name == 'StepAugmenter':
+        from .augment import StepAugmenter
+        return StepAugmenter
     if name == 'Engine':
         from .engine import Engine
         return Engine

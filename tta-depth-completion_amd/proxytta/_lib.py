@@ -106,6 +106,17 @@ class ScoreArgs(ctypes.Structure):             # include/ptta.h ptta_score_args
                 [(n, c_void_p) for n in ('state', 'batch_out', 'sample_out', 'sample_count_out')])
 
 
+class AugmentArgs(ctypes.Structure):           # include/ptta.h ptta_augment_args
+    _fields_ = ([(n, c_void_p) for n in ('image', 'sparse_depth', 'validity_map', 'ground_truth', 'loss_image', 'sparse_depth_out',
+                                         'validity_map_out', 'ground_truth_out', 'image1', 'draws')] +
+                [(n, c_int) for n in ('n', 'height', 'width', 'crop_height', 'crop_width', 'image_bilinear', 'scale_depth', 'pass2')] +
+                [('scratch', c_void_p), ('scratch_bytes', c_int64)])
+
+
+# ptta_augment_draw `flags`
+PTTA_AUG_HFLIP, PTTA_AUG_VFLIP, PTTA_AUG_ROTATE, PTTA_AUG_RESIZE = 1, 2, 4, 8
+PTTA_AUG_BRIGHTNESS, PTTA_AUG_CONTRAST, PTTA_AUG_GAMMA, PTTA_AUG_HUE, PTTA_AUG_SATURATION = 16, 32, 64, 128, 256
+
 # ptta_score_args `rule`, the largest max_n a score state is sized for
 PTTA_SCORE_RULE_ADAPT, PTTA_SCORE_RULE_VALIDATE = 0, 1
 PTTA_SCORE_MAX_N = 4096
@@ -186,6 +197,8 @@ SIGNATURES = [
     ('ptta_remove_patches', c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     ('ptta_crop_pad', c_int, [_P, _P, c_int, c_int, c_int, c_int] + [_P] * 7 + [c_int, c_float, _P]),
     ('ptta_resize_pad', c_int, [_P, _P, c_int, c_int, c_int, c_int] + [_P] * 5 + [c_int, c_int, c_float, _P]),
+    ('ptta_augment_scratch_bytes', c_int64, [c_int, c_int, c_int]),
+    ('ptta_augment_frames', c_int, [POINTER(AugmentArgs), _P]),
     ('ptta_set_stat_sync', c_int, [_P, _P, _P, _P, c_int64, c_int]),
     ('ptta_rccl_unique_id', c_int, [_P]),
     ('ptta_rccl_comm_create', c_int, [_P, c_int, c_int, POINTER(c_void_p)]),
@@ -277,5 +290,5 @@ def ptr(t):
     return c_void_p(t.data_ptr())
 
 
-__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs', 'HnGemmArgs', 'HnMomentsArgs', 'SummaryArgs', 'ScoreArgs',
+__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs', 'HnGemmArgs', 'HnMomentsArgs', 'SummaryArgs', 'ScoreArgs', 'AugmentArgs',
            'LOSS_FWD', 'LOSS_BWD', 'CONV_IN_FORMS', 'SIGNATURES', 'LIB_PATH', 'byref']

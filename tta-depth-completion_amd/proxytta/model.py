@@ -818,9 +818,14 @@ class ExternalModel_Adapt(object):
         return self.model.step(image, sparse_depth, validity_map, loss_image, want_depth, next_frame=next_frame)
 
     def adapt(self, image, sparse_depth, inner_iter=1, validity_map=None, loss_image=None, next_frame=None, ground_truth=None, score=None,
-              sink=None, sink_paths=None):
+              sink=None, sink_paths=None, augmenter=None, augmentation_probability=0.0, generator=None):
         """Per-frame adaptation = inner_iter steps then the scored eval forward
         (src/tta_main.py:579-636 and :729-736).  Returns (depth, loss_info of the last step).
+        augmenter (a proxytta.augment.StepAugmenter): the reference's operating mode (src/tta_main.py:581-633).  Every one of the inner_iter
+        iterations starts from the frame AS PASSED, draws a fresh geometric and photometric transform at augmentation_probability (from
+        `generator`, or torch's global one, and numpy's global state), and steps on the jittered image with the geometrically transformed
+        one as the loss image and the transformed sparse depth / validity map.  The scored forward, score and sink see the frame as passed.
+        Not together with loss_image (the augmenter makes it) or next_frame (see the message).
         next_frame = (image, sparse_depth) the next call will pass: announced to the LAST step of this frame (frame pipelining).
         ground_truth and score (a proxytta.score.RunScore), given together: score.update(depth, ground_truth) is enqueued behind the scored
         forward on the same stream (src/tta_main.py:769-798 without its copy to the host); the return value is the same.
@@ -828,7 +833,16 @@ class ExternalModel_Adapt(object):
         score's update when there is one): the prediction leaves as the 16-bit map save_depth stores; the return value is the same."""
         if (ground_truth is None) != (score is None):
             raise ValueError('adapt: ground_truth and score are given together or not at all')
-        depth, info = self._adapt(image, sparse_depth, inner_iter, validity_map, loss_image, next_frame)
+        if augmenter is not None:
+            if loss_image is not None:
+                raise ValueError('adapt: loss_image and augmenter are not given together: the augmenter makes the loss image (the geometrically '
+                                 'transformed, not jittered frame)')
+            if next_frame is not None:
+                raise ValueError('adapt: next_frame and augmenter are not given together: the look-ahead prefix would be computed on the frame as '
+                                 'announced, and the next call replaces that frame by its augmented form before it steps')
+            depth, info = self._adapt_augmented(image, sparse_depth, inner_iter, validity_map, augmenter, augmentation_probability, generator)
+        else:
+            depth, info = self._adapt(image, sparse_depth, inner_iter, validity_map, loss_image, next_frame)
         if score is not None:
             score.update(depth, ground_truth)
         if sink is not None:
@@ -850,6 +864,18 @@ class ExternalModel_Adapt(object):
             eng = self.model._engine(image)
             if getattr(eng.lib, 'ptta_forward_eval_last', None) is not None and not eng_is_padded(eng):
                 return eng.forward_eval_last(), info
+        depth = self.model.forward(image, sparse_depth, loss_type=CANONICAL_LOSS_TYPE)
+        return depth, info
+
+    def _adapt_augmented(self, image, sparse_depth, inner_iter, validity_map, augmenter, probability, generator):
+        info = None
+        self.model.train()
+        n, _, h, w = image.shape
+        for _ in range(inner_iter):                 # each iteration from the originals (src/tta_main.py:581 re-unpacks `inputs`)
+            augmenter.draw(n, h, w, probability, generator)
+            image1, loss_image, sparse1, validity1, _gt = augmenter.apply(image, sparse_depth, validity_map)
+            info, _ = self.model.step(image1, sparse1, validity1, loss_image)
+        self.model.eval()
         depth = self.model.forward(image, sparse_depth, loss_type=CANONICAL_LOSS_TYPE)
         return depth, info
 
