@@ -1141,6 +1141,62 @@ int ptta_op_hn_moments(const ptta_hn_moments_args* a, ptta_stream s);
 int ptta_op_hn_untile(const void* src_tiled, float* dst, long long r, ptta_stream s);
 int ptta_op_head_bwd_finish(const double* k12, const float* W0, const float* P, const float* X, long long r, void* dX, int halves, int dx_bf16,
                             ptta_stream s);
+/* Test hooks: the update half of a step stand-alone -- weight gradients and the optimizer -- launched through the launchers of
+ * csrc/ptta_kernels.h (csrc/ptta_ops_update.hip; tests/test_gpu_update_elementwise.py).  Every pointer is device memory unless it says
+ * host.  Partial buffers and device tables are allocated and freed inside the call.  All of them synchronise; -12 out of memory, -5 a HIP
+ * error.  The launchers dereference what they are given, so every hook refuses (-22) a NULL required pointer and a size below 1 before its
+ * first launch; past that it returns -22 exactly where its launcher does.
+ *
+ * ptta_op_wgrad32 (ptta_launch_wgrad32: wgrad32_kernel<float> / <bf16> + wgrad32_reduce_kernel): weight and bias gradient of a stride-1 3x3
+ * convolution of 32 -> 32 channels, zero padding 1.  x, gy: dense NHWC maps [b][h][w][32], both fp32 or (bf16 != 0) both bf16.  gw: element
+ * (co, ci, tap) at gw[co * co_stride + ci * 9 + tap], tap = 3 ky + kx -- co_stride = 288 is a dense [32][32][3][3] weight, 9 * Ci a group of
+ * 32 input channels inside a [32][Ci][3][3] weight (pass gw already offset by 9 * first channel); the other elements are not touched.
+ * gb [32] or NULL.  The launcher itself refuses nothing; -22 from the hook: co_stride < 288, b * h * w * 32 above 2e9 elements.
+ *
+ * ptta_op_gwgrad_view (ptta_launch_gwgrad_mfma): the same gradient for ci -> co channels on strided views.  x: fp32, pixel stride ldx >= ci
+ * ELEMENTS, the pointer already offset to the view's first channel; gy likewise with ldg >= co, fp32 or (gy_bf16) bf16 elements.  gw
+ * [co][ci][3][3] dense, gb [co] or NULL.  Adam inside the reduction when pw != NULL: pw, mw, vw [co][ci][3][3] and, unless pb == NULL, pb,
+ * mb, vb [co]; hyper = {lr, beta1, beta2, eps, weight_decay} fp32; step one int (the count BEFORE this update; the call leaves step + 1);
+ * ticket one unsigned that is 0 and comes back 0.  -22 from the launcher: gy_bf16 at a shape without a bf16x3 form that takes bf16
+ * gradients (the forms: ci, co <= 64, or ci <= 32 and co <= 128, or ci <= 128 and co <= 32, each with ci > 16); an Adam block at anything
+ * but ci, co <= 32 with ci > 16.  -22 from the hook: ci or co above 256, ldx < ci, ldg < co, pw with mw, vw, hyper, step or ticket NULL,
+ * pb with mb or vb NULL.
+ *
+ * ptta_op_adam = ptta_launch_step_inc + ptta_launch_adam, the launcher of adam_kernel, as ptta_adam_step with explicit gradients: step becomes step + 1,
+ * then p, m, v [n] are updated with g [n] at that count.  ptta_op_adam_multi (ptta_launch_adam_multi: adam_multi_kernel) and
+ * ptta_op_ema_multi (ptta_launch_ema_multi: ema_multi_kernel) take HOST arrays of nt device pointers and sizes; the hook lays them out as
+ * the device PttaAdamEntry table with running offsets.  rep[k] (host; NULL = all 1): 0 = listed but without a gradient (p, m, v, g of that
+ * entry are not read or written), r > 1 = r consecutive updates with the same gradient at the counts (t - 1) r + 1 .. t r.  The launch
+ * leaves step + 1 and ticket 0.  ptta_op_ema_multi: p[k] = fl(fl(p[k] tau) + fl(g[k] omt)) with tau_dev = {tau, omt} two device floats.
+ * -22: nt < 1, n[k] < 1, rep[k] < 0, a NULL pointer of an entry with rep != 0 (g may not be NULL for rep != 0).
+ *
+ * ptta_op_linear_wgrad (ptta_launch_linear_wgrad: linear_wgrad_kernel<NT, GPRO, XPRO> + wgrad_reduce_kernel): dW [O][I] = sum_r G'[r][o]
+ * X'[r][i], db [O] (may be NULL) = sum_r G'[r][o] over dense row-major G [R][O], X [R][I].  Gh != NULL (GPRO): G' = gscale (G - gc1 -
+ * (Gh - gmean) ginv gc2), the BatchNorm-backward transform with per-column tables [O]; xscale != NULL (XPRO): X' = relu(X xscale + xshift),
+ * tables [I].  -22 from the launcher: O % 128 != 0, I neither 32 nor a multiple of 128, R < 1, xscale with I = 32.  -22 from the hook: O < 1 or
+ * I < 1, Gh with a NULL table, xscale without xshift.
+ * ptta_op_glinear_wgrad (ptta_launch_glinear_wgrad: glinear_wgrad_kernel): gw [O][I] = sum_r gy[r][o] x[r][i], gb [O] or NULL, x [R][ldx]
+ * with ldx >= I and gy [R][ldg] with ldg >= O, fp32, any I, O >= 1.  -22 from the launcher: R < 1, gw NULL; from the hook: I < 1, O < 1,
+ * ldx < I, ldg < O, R above 2e9 (the launcher's views count rows in an int). */
+int ptta_op_wgrad32(const void* x_nhwc, const void* gy_nhwc, int bf16, int b, int h, int w, float* gw, float* gb, int co_stride, ptta_stream s);
+typedef struct ptta_gwgrad_view_args {
+    int b, h, w, ci, co, ldx, ldg, gy_bf16;
+    const float* x; const void* gy; float* gw; float* gb;
+    float* pw; float* mw; float* vw; float* pb; float* mb; float* vb; const float* hyper; int* step; unsigned* ticket;
+} ptta_gwgrad_view_args;
+int ptta_op_gwgrad_view(const ptta_gwgrad_view_args* a, ptta_stream s);
+int ptta_op_adam(float* p, float* m, float* v, const float* g, long long n, const float* hyper, int* step, ptta_stream s);
+int ptta_op_adam_multi(int nt, float* const* p, float* const* m, float* const* v, const float* const* g, const long long* n, const int* rep,
+                       const float* hyper, int* step, unsigned* ticket, ptta_stream s);
+int ptta_op_ema_multi(int nt, float* const* p, const float* const* g, const long long* n, const float* tau_dev, ptta_stream s);
+typedef struct ptta_linear_wgrad_args {
+    long long r;
+    int o, i;
+    const float* G; const float* Gh; const float* gscale; const float* gc1; const float* gc2; const float* gmean; const float* ginv;
+    const float* X; const float* xscale; const float* xshift; float* dW; float* db;
+} ptta_linear_wgrad_args;
+int ptta_op_linear_wgrad(const ptta_linear_wgrad_args* a, ptta_stream s);
+int ptta_op_glinear_wgrad(const float* x, int ldx, int i, const float* gy, int ldg, int o, long long r, float* gw, float* gb, ptta_stream s);
 /* Diagnostic (tools/bench_chain.py): `reps` dependent launches of one stride-1 32->32 convolution (fp32 NHWC, default arithmetic) captured
  * into one hipGraph and replayed `replays` times: microseconds per launch INSIDE a replayed graph.  epi_flags: 2 = ReLU mask from `aux`,
  * 4 = skip addition of `aux`, 8 = the same chain launched directly (no graph), 16 = the layer loop (ONE launch per `reps` layers with a

@@ -93,6 +93,16 @@ class HnMomentsArgs(ctypes.Structure):         # include/ptta.h ptta_hn_moments_
                 [(n, c_void_p) for n in ('X', 'W0', 'b0', 'part', 'gamma', 'beta', 'rm', 'rv', 'nbt', 'mean', 'inv', 'scale', 'shift')])
 
 
+class GwgradViewArgs(ctypes.Structure):        # include/ptta.h ptta_gwgrad_view_args
+    _fields_ = ([(n, c_int) for n in ('b', 'h', 'w', 'ci', 'co', 'ldx', 'ldg', 'gy_bf16')] +
+                [(n, c_void_p) for n in ('x', 'gy', 'gw', 'gb', 'pw', 'mw', 'vw', 'pb', 'mb', 'vb', 'hyper', 'step', 'ticket')])
+
+
+class LinearWgradArgs(ctypes.Structure):       # include/ptta.h ptta_linear_wgrad_args
+    _fields_ = ([('r', ctypes.c_longlong), ('o', c_int), ('i', c_int)] +
+                [(n, c_void_p) for n in ('G', 'Gh', 'gscale', 'gc1', 'gc2', 'gmean', 'ginv', 'X', 'xscale', 'xshift', 'dW', 'db')])
+
+
 class SummaryArgs(ctypes.Structure):           # include/ptta.h ptta_summary_args
     _fields_ = ([(n, c_int) for n in ('n_show', 'height', 'width', 'n_images', 'rows', 'normalize', 'out_dtype')] + [('max_predict_depth', c_float)] +
                 [('rev_mean', c_float * 3), ('rev_std', c_float * 3), ('image', c_void_p * 8), ('image_div255', c_void_p * 8)] +
@@ -246,6 +256,13 @@ SIGNATURES = [
     ('ptta_op_hn_moments', c_int, [POINTER(HnMomentsArgs), _P]),
     ('ptta_op_hn_untile', c_int, [_P, _P, ctypes.c_longlong, _P]),
     ('ptta_op_head_bwd_finish', c_int, [_P, _P, _P, _P, ctypes.c_longlong, _P, c_int, c_int, _P]),
+    ('ptta_op_wgrad32', c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
+    ('ptta_op_gwgrad_view', c_int, [POINTER(GwgradViewArgs), _P]),
+    ('ptta_op_adam', c_int, [_P, _P, _P, _P, ctypes.c_longlong, _P, _P, _P]),
+    ('ptta_op_adam_multi', c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ('ptta_op_ema_multi', c_int, [c_int, _P, _P, _P, _P, _P]),
+    ('ptta_op_linear_wgrad', c_int, [POINTER(LinearWgradArgs), _P]),
+    ('ptta_op_glinear_wgrad', c_int, [_P, c_int, c_int, _P, c_int, c_int, ctypes.c_longlong, _P, _P, _P]),
     ('ptta_version', c_int, []),
 ]
 
@@ -290,5 +307,5 @@ def ptr(t):
     return c_void_p(t.data_ptr())
 
 
-__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs', 'HnGemmArgs', 'HnMomentsArgs', 'SummaryArgs', 'ScoreArgs', 'AugmentArgs',
+__all__ = ['load', 'check', 'ptr', 'Hparams', 'GbnArgs', 'GbnView', 'CdSbnArgs', 'CD_OPS', 'PlaneArg', 'ConvInArgs', 'ConvOut1Args', 'LossArgs', 'HnGemmArgs', 'HnMomentsArgs', 'GwgradViewArgs', 'LinearWgradArgs', 'SummaryArgs', 'ScoreArgs', 'AugmentArgs',
            'LOSS_FWD', 'LOSS_BWD', 'CONV_IN_FORMS', 'SIGNATURES', 'LIB_PATH', 'byref']

@@ -619,6 +619,77 @@ def op_gwgrad(x_nhwc, gy_nhwc, impl='default', with_bias=True, reps=0):
     return gw, gb, (us.value if reps > 0 else None)
 
 
+def _update_rc(rc, what):
+    if rc != 0:
+        raise RuntimeError('%s failed (%d)' % (what, rc))
+
+
+def op_wgrad32(x, gy, b, h, w, gw, gb=None, co_stride=288, bf16=False):
+    """Test hook (include/ptta.h ptta_op_wgrad32; csrc/wgrad_adam.hip): the 32 -> 32 weight gradient of NHWC maps [b, h, w, 32] (fp32, or
+    int16 bf16 bit patterns with bf16) into gw (element (co, ci, tap) at co * co_stride + ci * 9 + tap behind gw's first element) and gb
+    [32] or None, in place."""
+    _update_rc(_lib.load().ptta_op_wgrad32(ptr(x), ptr(gy), int(bool(bf16)), int(b), int(h), int(w), ptr(gw), ptr(gb), int(co_stride), _stream()),
+               'ptta_op_wgrad32')
+
+
+def op_gwgrad_view(x, gy, b, h, w, ci, co, gw, gb=None, ldx=None, ldg=None, gy_bf16=False, adam=None):
+    """Test hook (include/ptta.h ptta_op_gwgrad_view; csrc/gwgrad_mfma.hip): the engine's weight-gradient launcher on strided views.  x, gy:
+    tensors whose first element is the view's first channel of pixel 0, pixel strides ldx / ldg elements (default: dense); gy fp32 or int16
+    bf16 bit patterns with gy_bf16.  adam: dict(pw, mw, vw, pb, mb, vb, hyper, step, ticket) for the Adam inside the reduction (pb, mb, vb
+    may be None)."""
+    a = _lib.GwgradViewArgs()
+    a.b, a.h, a.w, a.ci, a.co = int(b), int(h), int(w), int(ci), int(co)
+    a.ldx, a.ldg, a.gy_bf16 = int(ci if ldx is None else ldx), int(co if ldg is None else ldg), int(bool(gy_bf16))
+    for name, t in dict(adam or {}, x=x, gy=gy, gw=gw, gb=gb).items():
+        setattr(a, name, _pv(t))
+    _update_rc(_lib.load().ptta_op_gwgrad_view(byref(a), _stream()), 'ptta_op_gwgrad_view')
+
+
+def op_adam(p, m, v, g, hyper, step):
+    """Test hook (include/ptta.h ptta_op_adam; adam_kernel): step += 1, then one Adam update of p, m, v with g, in place.  hyper: five device
+    floats (lr, beta1, beta2, eps, weight_decay); step: one device int32."""
+    _update_rc(_lib.load().ptta_op_adam(ptr(p), ptr(m), ptr(v), ptr(g), p.numel(), ptr(hyper), ptr(step), _stream()), 'ptta_op_adam')
+
+
+def _host_table(entries, width):
+    cols = [(ctypes.c_void_p * len(entries))(*[None if e[j] is None else e[j].data_ptr() for e in entries]) for j in range(width)]
+    for e in entries:
+        assert all(t is None or (t.is_contiguous() and t.is_cuda) for t in e[:width])
+    return cols, (ctypes.c_longlong * len(entries))(*[e[0].numel() for e in entries])
+
+
+def op_adam_multi(entries, hyper, step, ticket):
+    """Test hook (include/ptta.h ptta_op_adam_multi; adam_multi_kernel): entries = [(p, m, v, g, rep)], every tensor updated in ONE launch;
+    step (device int32) goes up by one, ticket (device int32, 0) comes back 0."""
+    (p, m, v, g), n = _host_table(entries, 4)
+    rep = (c_int * len(entries))(*[int(e[4]) for e in entries])
+    _update_rc(_lib.load().ptta_op_adam_multi(len(entries), p, m, v, g, n, rep, ptr(hyper), ptr(step), ptr(ticket), _stream()), 'ptta_op_adam_multi')
+
+
+def op_ema_multi(entries, tau_dev):
+    """Test hook (include/ptta.h ptta_op_ema_multi; ema_multi_kernel): entries = [(target, online)], target = target tau + online (1 - tau)
+    in place, tau_dev = two device floats (tau, 1 - tau)."""
+    (p, g), n = _host_table(entries, 2)
+    _update_rc(_lib.load().ptta_op_ema_multi(len(entries), p, g, n, ptr(tau_dev), _stream()), 'ptta_op_ema_multi')
+
+
+def op_linear_wgrad(G, X, r, o, i, dW, db=None, **tables):
+    """Test hook (include/ptta.h ptta_op_linear_wgrad; csrc/head_train.hip): dW [o, i] and db [o] of G [r, o], X [r, i], in place.  tables:
+    Gh, gscale, gc1, gc2, gmean, ginv (the BatchNorm-backward transform of G) and xscale, xshift (BatchNorm + ReLU of X)."""
+    a = _lib.LinearWgradArgs()
+    a.r, a.o, a.i = int(r), int(o), int(i)
+    for name, t in dict(tables, G=G, X=X, dW=dW, db=db).items():
+        setattr(a, name, _pv(t))
+    _update_rc(_lib.load().ptta_op_linear_wgrad(byref(a), _stream()), 'ptta_op_linear_wgrad')
+
+
+def op_glinear_wgrad(x, ldx, i, gy, ldg, o, r, gw, gb=None):
+    """Test hook (include/ptta.h ptta_op_glinear_wgrad; csrc/ghead.hip): gw [o, i] and gb [o] of x [r, ldx] and gy [r, ldg] (views of i and
+    o columns), in place."""
+    _update_rc(_lib.load().ptta_op_glinear_wgrad(ptr(x), int(ldx), int(i), ptr(gy), int(ldg), int(o), int(r), ptr(gw), ptr(gb), _stream()),
+               'ptta_op_glinear_wgrad')
+
+
 def _nl_scratch(form, b, h, w, device):
     """The fixed-point forms' workspace (include/ptta.h ptta_nl_det_scratch_bytes); form 0 takes none."""
     if not form:
